@@ -10,14 +10,21 @@ HBM for the whole timed region.  The roofline object is solve_kernel's (the domi
 timed with HIP events the library records on the launch stream.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--horizon 20] [--dt 0.05]
+                  [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... --gpus N,
          or plain `python bench.py --gpus N`, which starts the N worker processes itself (RCCL)
+
+A plain run does what the headline needs and no more: set up, W warmup steps, the K timed steps, the outputs
+of the last timed step to DIR/<name>.npy if --dump-outputs is given, the line.  --full adds every other
+measurement to the same line (each can still be switched off by its own --no-* option): the cold-start pass
+('cold'), the configs[3] dataset leg ('dataset'), config 3 ('config3'), the end-to-end variant ('host_io'), the
+CPU baselines ('cpu_baseline'), KalmanNet ('knet') and the one-trajectory measurement ('config1').
 
 Multi-GPU: trajectories are independent, so each rank owns its own B trajectories (ids
 rank*B .. rank*B+B-1, weak scaling) with no data-path collective; the ranks only meet at the
 timing barriers and the max-over-ranks reduction of the elapsed time.
 
-Prints ONE JSON line (rank 0) with the metric, the roofline of the dominant kernel and the CPU
+Prints ONE JSON line (rank 0) with the metric and the roofline of the dominant kernel; with --full also the CPU
 baseline (the C oracle -- a restatement of the reference path -- on a bounded sample, host cores).
 """
 from __future__ import annotations
@@ -635,7 +642,17 @@ def parse_args(argv=None):
                     help="skip the end-to-end (H2D + run + D2H) variant of the headline ('host_io')")
     ap.add_argument("--dist-timeout", type=float, default=600.0,
                     help="seconds before a process-group rendezvous or collective gives up (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure everything else the line can carry (cold, dataset, config3, "
+                         "host_io, cpu_baseline, knet, config1); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step of the headline computed to DIR/<name>.npy (float64)")
     args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: the headline alone, whatever the per-leg options say
+        args.no_cold = args.no_cpu = args.no_knet = args.no_config1 = True
+        args.config3 = args.host_io = False
+        args.dataset_steps = 0
     # the profiles of another horizon (config 3's N = 40: traffic_r06_n40.json, sq_f64_r06_n40.json) when the
     # defaults are in use and such a file exists
     if args.horizon != 20:
@@ -884,14 +901,51 @@ def host_io_measure(args, ops, w, N, reps=3):
             "h2d_bytes_min": h2d, "reps": reps}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, s, warmup, steps):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step (t = warmup + steps - 1), as
+    float64 .npy files under `path`: x [B,6] (the plant state the step left) and u_cmd [B,2] (the command it applied)
+    -- the history rows the step wrote --, status [B] and iters [B]; and hist_x [B,k,6] / hist_u [B,k,2], the rows of
+    the last k timed steps, k as many as fit.  At most DUMP_MAX_BYTES in all: half for the last step (the first
+    trajectories of a batch too large for it), half for the histories.
+    Every written number is finite.  A trajectory whose solves fail keeps its last command, as the reference does
+    (mpc_6stati.py:257-262), and its Euler plant can then leave the range of float64 within a long run (the line's
+    solver_stats.status_hist counts its steps under status 6): finite [B] is 0.0 for a trajectory with a non-finite
+    value in any of the arrays and 1.0 otherwise, and such a trajectory's x, u_cmd, hist_x and hist_u rows (the
+    overflowing values and the 1e100s on the way there) are written as 0.0; its status and iters stay."""
+    os.makedirs(path, exist_ok=True)
+    t = warmup + steps - 1
+    B = int(s["hx"].shape[0])
+    nb = min(B, DUMP_MAX_BYTES // 2 // (11 * 8))
+    k = min(steps, DUMP_MAX_BYTES // 2 // (nb * 8 * 8))
+    arrays = {"x": s["hx"][:nb, t + 1], "u_cmd": s["hu"][:nb, t], "status": s["st"][t, :nb], "iters": s["it"][t, :nb]}
+    if k > 0:
+        arrays["hist_x"] = s["hx"][:nb, t + 2 - k:t + 2]
+        arrays["hist_u"] = s["hu"][:nb, t + 1 - k:t + 1]
+    arrays = {name: a.cpu().numpy().astype(np.float64) for name, a in arrays.items()}
+    finite = np.ones(nb)
+    for a in arrays.values():
+        finite[~np.isfinite(a).reshape(nb, -1).all(axis=1)] = 0.0
+    for name in set(arrays) - {"status", "iters"}:
+        arrays[name][finite == 0.0] = 0.0
+    arrays["finite"] = finite
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def bench_run(args, ops, dist, rank, world):
     """One rank's bench: warmup, the timed region bracketed by barrier + synchronize on both sides, the
-    max-over-ranks elapsed time, the dataset leg; rank 0 returns the JSON record (None elsewhere)."""
+    max-over-ranks elapsed time, the outputs of the last timed step (--dump-outputs) and, with --full, the other
+    legs; rank 0 returns the JSON record (None elsewhere)."""
     N, Ts, B = args.horizon, args.dt, args.batch
     fused = not args.per_step
     stall = args.stall_json if (N == 20 and B == 4096) else None    # (the profiled config)
     rec, s, w = mpc_leg(args, ops, dist, rank, world, N, args.kind, args.traffic_json, args.issue_json, stall,
                         with_cold=not args.no_cold)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, s, args.warmup, args.steps)
     dataset = dataset_leg(args, w, ops, dist, rank, world) if args.dataset_steps > 0 else None
     # config 3 (BASELINE.json configs[2]): 4096 mixed sinusoid / parabola references, N = 40, same K / W -- its own line
     # object beside the headline, measured by the same timed region (one GPU)

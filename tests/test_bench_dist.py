@@ -69,8 +69,8 @@ def _rank(rank, port, q, csv_dir, world=2):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     import bench
-    out = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--dataset-steps", "5",
-                      "--no-cpu", "--no-knet", "--dist-timeout", "120", "--dataset-csv", csv_dir],
+    out = bench.main(["--gpus", str(world), "--full", "--steps", "3", "--warmup", "1", "--batch", "4",
+                      "--dataset-steps", "5", "--no-cpu", "--no-knet", "--dist-timeout", "120", "--dataset-csv", csv_dir],
                      ops_factory=CpuOps, backend="gloo")
     q.put((rank, out))
 
@@ -130,8 +130,8 @@ def test_bench_world1_config3_host_io_and_profile_reasons(tmp_path, monkeypatch)
         monkeypatch.delenv(k, raising=False)
     bad = tmp_path / "sq.json"
     bad.write_text(json.dumps({"batch": 4, "horizon": 20, "f64_flop_issued_per_step": 1.0, "valu_insts_per_step": 1.0}))
-    out = bench.main(["--steps", "3", "--warmup", "1", "--batch", "4", "--dataset-steps", "0", "--no-cpu", "--no-knet",
-                      "--no-config1", "--config3-issue-json", str(bad), "--issue-json", str(bad),
+    out = bench.main(["--full", "--steps", "3", "--warmup", "1", "--batch", "4", "--dataset-steps", "0", "--no-cpu",
+                      "--no-knet", "--no-config1", "--config3-issue-json", str(bad), "--issue-json", str(bad),
                       "--traffic-json", str(tmp_path / "none.json")], ops_factory=CpuOps, backend="gloo")
     assert out["n_gpus"] == 1 and "H2D / D2H excluded" in out["config"]["timed_region"]
     assert out["roofline"]["issue"] is not None and out["roofline"]["issue"]["source"].endswith("sq.json")
@@ -141,3 +141,59 @@ def test_bench_world1_config3_host_io_and_profile_reasons(tmp_path, monkeypatch)
     assert c3["roofline"]["issue"] is None and "horizon = 20, this launch has 40" in c3["roofline"]["issue_rejected"]
     hio = out["host_io"]
     assert hio["value"] > 0 and hio["steps"] == 4 and hio["d2h_bytes"] == 4 * 5 * 6 * 8 + 4 * 4 * 2 * 8 + 2 * 4 * 4 * 4
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_last_step(tmp_path, monkeypatch):
+    """Without --full the line carries the headline and none of the other legs, whatever the per-leg options say;
+    --dump-outputs writes the last timed step's outputs (and the timed steps' history rows) as float64 .npy files,
+    the same from run to run."""
+    import bench
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4", "--dataset-steps", "5"]
+    outs = [bench.main(argv + ["--dump-outputs", str(tmp_path / d)], ops_factory=CpuOps, backend="gloo") for d in "ab"]
+    out = outs[0]
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["value"] == pytest.approx(4 * 3 / (out["ms_per_step"] * 3e-3))
+    assert all(out[k] == v for k, v in (("unit", "MPC steps/s"), ("higher_is_better", True), ("dtype", "f64")))
+    assert all(out.get(k) is None for k in ("cold", "dataset", "config3", "host_io", "cpu_baseline", "knet", "config1"))
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("x", "u_cmd", "status", "iters", "hist_x", "hist_u", "finite")}
+    assert all(a.dtype == np.float64 for a in got.values()) and (got["finite"] == np.ones(4)).all()
+    assert got["x"].shape == (4, 6) and got["u_cmd"].shape == (4, 2) and got["status"].shape == got["iters"].shape == (4,)
+    assert got["hist_x"].shape == (4, 3, 6) and got["hist_u"].shape == (4, 3, 2)
+    # CpuOps adds 0.01 per step: after 2 + 3 steps the state is x0 + 0.05, and the history's last row is that state
+    x0 = bench.make_workload(4, 20, 0.05, kind="spline", seed=0, id_offset=0)["x0"]
+    np.testing.assert_allclose(got["x"], x0 + 0.05, rtol=0, atol=1e-12)
+    np.testing.assert_array_equal(got["hist_x"][:, -1], got["x"])
+    np.testing.assert_allclose(got["hist_x"][:, 0], x0 + 0.03, rtol=0, atol=1e-12)
+    assert (got["iters"] == 25).all() and (got["status"] == 0).all()
+    for n, a in got.items():
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / f"{n}.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+
+
+def test_dump_outputs_writes_finite_numbers_and_flags_diverged_trajectories(tmp_path):
+    """A trajectory whose plant left the range of float64 (inf / nan in its rows) is flagged in finite.npy and its
+    state and command rows are written as 0 (status and iters stay); every other trajectory is written as it is."""
+    import bench
+    B, W, K = 3, 1, 4
+    T = W + K
+    g = torch.Generator().manual_seed(0)
+    s = dict(hx=torch.randn((B, T + 1, 6), dtype=torch.float64, generator=g),
+             hu=torch.randn((B, T, 2), dtype=torch.float64, generator=g),
+             st=torch.zeros((T, B), dtype=torch.int32), it=torch.full((T, B), 25, dtype=torch.int32))
+    s["hx"][1, T - 1, 3] = float("inf")       # an earlier timed step's row of trajectory 1
+    s["hx"][1, T, 0] = float("nan")           # its last row
+    s["hx"][1, T, 4] = -float("inf")
+    s["st"][T - 1, 1] = 6
+    want_hx = s["hx"].numpy().copy()
+    bench.dump_outputs(str(tmp_path), s, W, K)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["finite", "hist_u", "hist_x", "iters", "status", "u_cmd", "x"]
+    assert all(np.isfinite(a).all() and a.dtype == np.float64 for a in got.values())
+    assert got["finite"].tolist() == [1.0, 0.0, 1.0] and got["status"].tolist() == [0.0, 6.0, 0.0]
+    keep = np.array([1.0, 0.0, 1.0])
+    np.testing.assert_array_equal(got["x"], np.where(keep[:, None] > 0, want_hx[:, T], 0.0))
+    np.testing.assert_array_equal(got["hist_x"], np.where(keep[:, None, None] > 0, want_hx[:, W + 1:], 0.0))
+    np.testing.assert_array_equal(got["hist_u"], np.where(keep[:, None, None] > 0, s["hu"].numpy()[:, W:], 0.0))
+    np.testing.assert_array_equal(got["u_cmd"], np.where(keep[:, None] > 0, s["hu"].numpy()[:, T - 1], 0.0))
+    assert (got["iters"] == 25).all()

@@ -4,7 +4,7 @@
 #   gpurun --timeout 1200 -- 'tools/gpu_session.sh tests bench'
 # Steps (any order, each under its own time limit, chained: the first failure ends the session):
 #   tests       the -m gpu suite (pytest, thread timeouts)                     -> gpurun_out/$TAG_tests.log
-#   bench       the driver's command: bench.py --gpus 1 --steps 20 --warmup 5  -> gpurun_out/$TAG_bench.json
+#   bench       the whole line: bench.py --gpus 1 --steps 20 --warmup 5 --full -> $TAG_bench.json in the output folder
 #   cfg3        config 3: N = 40, mixed references, 20 steps                  -> gpurun_out/$TAG_n40.json
 #   phase       phase profile of the fused 20-step launch (tools/phase_profile.py) -> gpurun_out/$TAG_phase20.txt
 #   phase40     the same at N = 40 (config 3)                                  -> gpurun_out/$TAG_phase20_n40.txt
@@ -70,7 +70,7 @@ for step in "$@"; do
         tail -2 $O/${TAG}_tests.log
         [ $rc -eq 0 ] || { grep -E "FAILED|Error|assert" $O/${TAG}_tests.log | head -30; exit $rc; } ;;
     bench)
-        timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench.json \
+        timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench.json \
             2> $O/${TAG}_bench.err || { tail -5 $O/${TAG}_bench.err; exit 1; }
         python3 -c "import json;d=json.load(open('$O/${TAG}_bench.json'));print('value',d['value'],'cold',d['cold']['value'],'dataset',d['dataset']['traj_steps_per_s'],'knet',d['knet']['value'])" ;;
     cfg3)
@@ -93,7 +93,7 @@ for step in "$@"; do
     stall40) pmc_stall _n40 "$N40" 40 && echo ok || exit 1 ;;
     trace)
         timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $O/${TAG}_kt -o run --output-format csv -- \
-            python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_kt.log 2>&1 &&
+            python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_kt.log 2>&1 &&
         python3 tools/trace_dispatches.py $O/${TAG}_kt/run_kernel_trace.csv "solve_kernel<40, true, true" \
             $O/${TAG}_dispatches.json > /dev/null && echo ok || exit 1 ;;
     tiers)
