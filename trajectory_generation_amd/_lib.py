@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRAJMPC_LIB") or os.path.join(_HERE, "libtrajmpc.so")
 CSRC = os.path.join(_HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "trajmpc.h")
-HEADERS = [HEADER, os.path.join(os.path.dirname(_HERE), "include", "trajknet.h")]
+HEADERS = [HEADER, os.path.join(os.path.dirname(_HERE), "include", "trajknet.h"),
+           os.path.join(os.path.dirname(_HERE), "include", "trajgen.h")]
 
 TRAJ_OK, TRAJ_E_ARG, TRAJ_E_UNSUPPORTED, TRAJ_E_LAUNCH, TRAJ_E_HANDOFF = 0, -1, -2, -3, -4
 MAX_N = 40            # hot kernels, every entry point (include/trajmpc.h TRAJ_MAX_N)
@@ -80,6 +81,22 @@ class KnetNet(C.Structure):
             "gru_sigma_whh", "gru_sigma_bhh", "fc1_w", "fc1_b", "fc7_w", "fc7_b", "gru_s_wih", "gru_s_bih",
             "gru_s_whh", "gru_s_bhh", "fc3_w", "fc3_b", "fc4_w", "fc4_b", "innov_logit")] + [
         ("d_fc2h", C.c_int)] + [(k, C.c_void_p) for k in ("fc2a_w", "fc2a_b", "fc2b_w", "fc2b_b")]
+
+
+class GenConfig(C.Structure):
+    """traj_gen_config (include/trajgen.h: limits of generation_type1.py:251, :287-288, state clip of :81-82)."""
+    _fields_ = [
+        ("model", C.c_int), ("Ts", C.c_double),
+        ("u_lo", C.c_double * 2), ("u_hi", C.c_double * 2),
+        ("du_lo", C.c_double * 2), ("du_hi", C.c_double * 2),
+        ("clip_state", C.c_int), ("vx_min", C.c_double), ("omega_max", C.c_double),
+    ]
+
+
+GEN_MODEL_MPC, GEN_MODEL_TYPE1, GEN_MODEL_TYPE2 = 0, 1, 2   # TRAJ_GEN_MODEL_*
+GEN_STAGE_STEPS = 8                                          # TRAJ_GEN_STAGE_STEPS
+GEN_FORM_DEFAULT, GEN_FORM_STAGED, GEN_FORM_DIRECT = 0, 1, 2  # traj_gen_debug_store_form
+GEN_DEFAULT_FORM = GEN_FORM_DIRECT                           # TRAJ_GEN_DEFAULT_FORM
 
 
 class Paths(C.Structure):
@@ -150,6 +167,11 @@ _SIGS = {
                                              _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "traj_ekf_run_f64": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_double, C.c_int, C.c_int,
                                    _V, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_gen_abi_version": (C.c_int, []),
+    "traj_gen_default_config": (C.c_int, [C.POINTER(GenConfig), C.c_int, C.c_double]),
+    "traj_gen_simulate_batch": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(GenConfig), C.c_int, C.c_int, _V, _V,
+                                          _V, _V, _V]),
+    "traj_gen_debug_store_form": (C.c_int, [C.c_int]),
     "traj_closed_loop_step": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
                                         _V, _V, _V, C.c_int, C.c_int, _V, _V, _V, _V, _V, C.c_size_t, _V]),
     "traj_closed_loop_run": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
@@ -181,6 +203,8 @@ def lib():
             fn.argtypes = args
         if L.traj_abi_version() != 4:
             raise RuntimeError("libtrajmpc ABI version mismatch")
+        if L.traj_gen_abi_version() != 1:
+            raise RuntimeError("libtrajmpc generator ABI (include/trajgen.h) version mismatch")
         _lib = L
     return _lib
 
@@ -202,6 +226,12 @@ def default_params() -> VehicleParams:
 def default_config(N: int, Ts: float) -> MpcConfig:
     c = MpcConfig()
     check(lib().traj_default_config(C.byref(c), int(N), float(Ts)), "traj_default_config")
+    return c
+
+
+def default_gen_config(model: int, Ts: float) -> GenConfig:
+    c = GenConfig()
+    check(lib().traj_gen_default_config(C.byref(c), int(model), float(Ts)), "traj_gen_default_config")
     return c
 
 

@@ -10,6 +10,7 @@ Reference correspondence (DorianaG01/trajectory_generation):
   mpc_qp_batch                                       the QP half :180-275 with caller (A, B, g)
   ref_window_batch / PathSet                         MPC/main.py:51-68 (geometry: DESIGN.md)
   closed_loop_step / run_closed_loop                 MPC/main.py:85-101, B trajectories at once
+  simulate_open_loop                                 generation_traj/generation_type1.py:70-84, :131-137, :287-288
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MpcConfig, Paths, VehicleParams
+from ._lib import GenConfig, MpcConfig, Paths, VehicleParams
 
 REFERENCE_PARAMS = {
     "Cm1": 0.287, "Cm2": 0.0545, "Cr0": 0.0518, "Cr2": 0.00035,
@@ -138,6 +139,51 @@ def lateral_error_batch(X, Y, Xref, Yref, phiref) -> torch.Tensor:
     _lib.check(_lib.lib().traj_lateral_error_batch(ts[0].shape[0], *[_p(t) for t in ts], _p(out), _stream()),
                "traj_lateral_error_batch")
     return out
+
+
+# ---------------------------------------------------------------- open-loop generators (include/trajgen.h)
+
+def gen_config_struct(model=_lib.GEN_MODEL_TYPE1, Ts=0.01, u_bounds=None, du_bounds=None, clip_state=None,
+                      vx_min=None, omega_max=None) -> GenConfig:
+    """traj_gen_config: the model's defaults (traj_gen_default_config) with the given fields replaced.
+    u_bounds / du_bounds: ((d_lo, d_hi), (delta_lo, delta_hi)) as generation_type1.py:251 writes them;
+    a channel with du_bounds (-inf, inf) has no slew limiter."""
+    c = _lib.default_gen_config(int(model), float(Ts))
+    for ch in range(2):
+        if u_bounds is not None:
+            c.u_lo[ch], c.u_hi[ch] = (float(v) for v in u_bounds[ch])
+        if du_bounds is not None:
+            c.du_lo[ch], c.du_hi[ch] = (float(v) for v in du_bounds[ch])
+    if clip_state is not None:
+        c.clip_state = int(bool(clip_state))
+    if vx_min is not None:
+        c.vx_min = float(vx_min)
+    if omega_max is not None:
+        c.omega_max = float(omega_max)
+    return c
+
+
+def simulate_open_loop(x0, u_raw, gen_cfg: GenConfig, params=None) -> dict:
+    """B open-loop trajectories in one launch (traj_gen_simulate_batch): slew limiter and output clip of
+    generation_type1.py:131-137, :287-288 on u_raw [B,T,2], then the Euler loop of :70-84 from x0 [B,6].
+    Returns torch.cuda tensors X [B,T+1,6] (X[:,0] = x0) and U [B,T,2] (the controls that were applied)."""
+    x0 = _dev(x0, (-1, 6))
+    B = x0.shape[0]
+    u_raw = _dev(u_raw, None, x0.device)
+    if u_raw.dim() != 3 or u_raw.shape[0] != B or u_raw.shape[2] != 2:
+        raise ValueError(f"u_raw must be [B,T,2] with B = {B}, got {tuple(u_raw.shape)}")
+    T = u_raw.shape[1]
+    X = torch.empty((B, T + 1, 6), dtype=torch.float64, device=x0.device)
+    U = torch.empty((B, T, 2), dtype=torch.float64, device=x0.device)
+    _lib.check(_lib.lib().traj_gen_simulate_batch(C.byref(params_struct(params)), C.byref(gen_cfg), B, T, _p(x0),
+                                                  _p(u_raw), _p(X), _p(U), _stream()), "traj_gen_simulate_batch")
+    return dict(X=X, U=U)
+
+
+def set_gen_store_form(form: int) -> None:
+    """Experiments and tests: the kernel form of the following simulate_open_loop calls (_lib.GEN_FORM_DEFAULT /
+    GEN_FORM_STAGED / GEN_FORM_DIRECT, traj_gen_debug_store_form).  Results do not depend on it."""
+    _lib.check(_lib.lib().traj_gen_debug_store_form(int(form)), "traj_gen_debug_store_form")
 
 
 # ---------------------------------------------------------------- MPC step

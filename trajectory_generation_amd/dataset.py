@@ -16,6 +16,9 @@ Sharding: rank r owns trajectory ids [r B, (r+1) B) (ids and per-trajectory seed
 result does not depend on the rank count); the only collective is the final gather of the histories
 to rank 0 over RCCL (dist.gather of one fixed-size [B,T+1,9] block per rank; the other ranks receive
 nothing), after which rank 0 writes the CSVs.
+
+generate_open_loop is the same flow for the reference's own open-loop generator (generation_type1.py:240-339,
+one kernel launch per rank), and merge_datasets is generation_traj/merge_datasets.py on the files' text.
 """
 from __future__ import annotations
 
@@ -178,6 +181,76 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
     if out_prefix is not None:
         _write_with_sidecar(out_prefix, X, U, st, np.arange(X.shape[0]), Ts, drop_failed)
     return X, U, st
+
+
+def generate_open_loop(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shards=False):
+    """The reference's own dataset (generation_traj/generation_type1.py:240-339), B trajectories of T steps per rank:
+    this rank's ids rank * B .. rank * B + B - 1 of the dataset seeded with `seed` (generation_type1.generate_steps:
+    host draw, one kernel launch), gathered to rank 0, which writes ``{out_prefix}_clean.csv`` /
+    ``{out_prefix}_noisy.csv`` (write_csv).  No status sidecar: the reference has none and no step can fail.
+    shards: no gather, every rank writes ``{out_prefix}_rank{r}_*.csv`` with its global ids.
+    Returns (X [W B,T+1,6], U [W B,T,2]) on rank 0 and None on the other ranks (shards: this rank's share)."""
+    import torch
+    from .generation_type1 import generate_steps
+    rank = dist.get_rank() if (dist is not None and dist.is_initialized()) else 0
+    res = generate_steps(B, T, Ts, seed=seed, id_offset=rank * B)
+    X, U = res["X"], res["U"]
+    if shards:
+        if out_prefix is not None:
+            write_csv(f"{out_prefix}_rank{rank}", X.cpu().numpy(), U.cpu().numpy(), res["ids"], Ts)
+        return X, U
+    status = torch.zeros((T, B), dtype=torch.int32, device=X.device)
+    blk = gather_to_root(pack_history(X, U, status), dist)
+    if blk is None:
+        return None
+    X, U, _ = unpack_history(blk)
+    if out_prefix is not None:
+        write_csv(out_prefix, X.cpu().numpy(), U.cpu().numpy(), np.arange(X.shape[0]), Ts)
+    return X, U
+
+
+def merge_datasets(first_prefix, second_prefix, out_prefix):
+    """generation_traj/merge_datasets.py:33-70 for ``{prefix}_clean.csv`` / ``{prefix}_noisy.csv`` pairs: the second
+    pair's trajectory ids are shifted by id_offset = max(trajectory_id of the first clean file) + 1 and appended to
+    the first pair's rows, into ``{out_prefix}_clean.csv`` / ``{out_prefix}_noisy.csv``.
+
+    The merge works on the text: the first file's lines are copied verbatim and the second file's lines with only
+    their last field (trajectory_id) rewritten, so no float passes through a parse / print round trip (the
+    reference's read_csv -> to_csv can move last digits).  Raises ValueError if a file is missing, the two headers of
+    a pair differ, or the last column is not trajectory_id.  Returns id_offset."""
+    import os
+
+    def read(path):
+        if not os.path.exists(path):
+            raise ValueError(f"merge_datasets: file not found: {path}")
+        with open(path, newline="") as f:
+            lines = f.read().split("\n")
+        if lines and lines[-1] == "":
+            lines.pop()
+        if not lines or lines[0].rstrip("\r").split(",")[-1] != "trajectory_id":
+            raise ValueError(f"merge_datasets: {path}: the last column must be trajectory_id")
+        return lines[0], lines[1:]
+
+    def last_id(line):
+        return int(float(line.rstrip("\r").rpartition(",")[2]))
+
+    pairs = {}
+    for kind in ("clean", "noisy"):
+        h1, b1 = read(f"{first_prefix}_{kind}.csv")
+        h2, b2 = read(f"{second_prefix}_{kind}.csv")
+        if h1 != h2:
+            raise ValueError(f"merge_datasets: the {kind} files' headers differ: {h1!r} / {h2!r}")
+        pairs[kind] = (h1, b1, b2)
+    id_offset = max((last_id(ln) for ln in pairs["clean"][1]), default=-1) + 1
+    for kind, (header, b1, b2) in pairs.items():
+        eol = "\r" if header.endswith("\r") else ""
+        with open(f"{out_prefix}_{kind}.csv", "w", newline="") as f:
+            f.write(header + "\n")
+            f.writelines(ln + "\n" for ln in b1)
+            for ln in b2:
+                head, _, _ = ln.rstrip("\r").rpartition(",")
+                f.write(f"{head},{last_id(ln) + id_offset}{eol}\n")
+    return id_offset
 
 
 def _write_with_sidecar(prefix, X, U, st, ids, Ts, drop_failed):
