@@ -12,6 +12,8 @@
  *   generation_type1.py:38-68   tire_forces / f_cont   TRAJ_GEN_MODEL_TYPE1
  *   generation_type2.py:52-86   tire_forces / f_cont   TRAJ_GEN_MODEL_TYPE2
  *   generation_type2.py:180-187 integration loop       TRAJ_GEN_MODEL_TYPE2 with given controls
+ *   generation_type2.py:95-157  sample_controls_piecewise   traj_gen_piecewise_batch (controller, its
+ *                               + :180-187                  numpy random stream and the integration)
  *
  * Conventions are trajmpc.h's: device pointers, row-major float64, asynchronous on `stream`
  * (a hipStream_t, NULL = default stream), no allocation and no host synchronization (capturable in
@@ -74,6 +76,85 @@ int traj_gen_simulate_batch(const traj_vehicle_params* p, const traj_gen_config*
 #define TRAJ_GEN_STAGE_STEPS 8
 #define TRAJ_GEN_DEFAULT_FORM 2
 int traj_gen_debug_store_form(int form);
+
+/* ---- generation_type2.py:95-157, :180-187: the piecewise (state-machine) generator, whole on the GPU ----
+ *
+ * sample_controls_piecewise is a feedback controller: it draws a driving mode, a segment length and the
+ * segment's controls from np.random.default_rng(seed + i), and reads the speed of a shadow simulation at
+ * every segment start and every step.  The shadow simulation and the ground-truth integration of :180-187
+ * are the same arithmetic on the same inputs, so one integration per lane serves both.  The random stream
+ * is numpy's Generator(PCG64), reproduced in the kernel (csrc/gen_rng.h); the caller supplies each
+ * trajectory's generator state, np.random.PCG64(seed + i).state, as four uint64
+ * (state >> 64, state & (2^64 - 1), inc >> 64, inc & (2^64 - 1)). */
+
+/* The rules of generation_type2.py:22-30 that the controller reads, and the two mode distributions of
+ * :109-112 as cumulative sums, cdf = p.cumsum() / p.cumsum()[-1] (what Generator.choice searches). */
+typedef struct {
+    double v_turn_max, v_high;          /* 1.2, 4.0                                                     */
+    double d_range[2];                  /* (0.0, 0.33)                                                  */
+    double delta_turn_range[2];         /* (0.015, 0.04)                                                */
+    double delta_straight_noise;        /* 0.004                                                        */
+    double cdf_after_turn[2];           /* accelerate, cruise:                         p = .5 .5        */
+    double cdf_any[4];                  /* accelerate, cruise, turn_left, turn_right:  p = .35 .35 .15 .15 */
+} traj_gen_fsm_rules;
+
+/* The controller's constants (generation_type2.py:97, :101, :114, :120-124, :131-133, :142). */
+#define TRAJ_FSM_DELTA_RATE_MAX 0.30   /* steering rate limit, rad/s                                    */
+#define TRAJ_FSM_V_FLOOR        0.35   /* below it d is raised to TRAJ_FSM_D_BOOST_MIN, for good        */
+#define TRAJ_FSM_D_BOOST_MIN    0.15
+#define TRAJ_FSM_V_STALL        0.5    /* below it at a segment start: the stall override               */
+#define TRAJ_FSM_STALL_D_LO     0.5
+#define TRAJ_FSM_STALL_D_HI     1.0
+#define TRAJ_FSM_STALL_SEG      0.3    /* the overridden segment lasts at least rint(0.3 / Ts) steps    */
+#define TRAJ_FSM_SEG_LO         0.4    /* segment length, seconds: uniform(0.4, 1.5)                    */
+#define TRAJ_FSM_SEG_HI         1.5
+#define TRAJ_FSM_ACCEL_D_LO     0.3    /* accelerate: d = uniform(0.3, d_range[1])                      */
+#define TRAJ_FSM_CRUISE_D_LO    (-0.05)
+#define TRAJ_FSM_CRUISE_D_HI    0.2
+#define TRAJ_FSM_TURN_FAST_D_LO 0.0    /* turn entered with v > v_turn_max                              */
+#define TRAJ_FSM_TURN_FAST_D_HI 0.15
+#define TRAJ_FSM_TURN_D_LO      0.05
+#define TRAJ_FSM_TURN_D_HI      0.25
+#define TRAJ_FSM_DELTA_CLIP     0.6
+
+/* Mode codes of the mode[B,T] output. */
+#define TRAJ_FSM_ACCELERATE 0
+#define TRAJ_FSM_CRUISE     1
+#define TRAJ_FSM_TURN_LEFT  2
+#define TRAJ_FSM_TURN_RIGHT 3
+
+/* ControlRules() of generation_type2.py:22-30 and the cdfs of its two choice calls.  TRAJ_E_ARG: null. */
+int traj_gen_fsm_default_rules(traj_gen_fsm_rules* r);
+
+/* B trajectories of T steps, one lane per trajectory, the whole walk in one launch.  Per trajectory:
+ * sample_controls_piecewise(T, cfg->Ts, x0, params, rules) on the stream rng_state[b], its shadow state
+ * being the trajectory itself: U[k] is the command of step k, X[k+1] = X[k] + Ts f2(X[k], U[k]) with the
+ * state clip of cfg (vx_min, omega_max, as traj_gen_simulate_batch applies it), mode[k] the segment's
+ * label after relabelling.  cfg->model must be TRAJ_GEN_MODEL_TYPE2; the limits of cfg (u_lo .. du_hi) are
+ * not read: the controller has its own (d_range, TRAJ_FSM_DELTA_CLIP, TRAJ_FSM_DELTA_RATE_MAX).
+ * rng_state_out (may be NULL): each stream's state after its last draw, in the layout of rng_state.
+ * TRAJ_E_ARG: null pointer (data pointers only when B > 0), B < 0, T < 1, another model, Ts not finite or
+ * not positive, a cdf that does not end at 1.0.  B == 0: TRAJ_OK, no launch.  Nothing outside X[B,T+1,6],
+ * U[B,T,2], mode[B,T] and rng_state_out[B,4] is written. */
+int traj_gen_piecewise_batch(const traj_vehicle_params* p, const traj_gen_config* cfg,
+                             const traj_gen_fsm_rules* rules, int B, int T, const double* x0 /*[B,6]*/,
+                             const unsigned long long* rng_state /*[B,4]*/, double* X /*[B,T+1,6]*/,
+                             double* U /*[B,T,2]*/, unsigned char* mode /*[B,T]*/,
+                             unsigned long long* rng_state_out /*[B,4] or NULL*/, void* stream);
+
+/* For the tests of csrc/gen_rng.h and for nothing else: n draws of one kind from a stream.
+ * kind: 0 raw 64-bit words (out is uint64), 1 doubles in [0, 1), 2 standard normals (out is double).
+ * _host runs the header on the CPU (host pointers, synchronous); _batch runs it on the GPU, lane b drawing
+ * out[b, 0..n) from states[b] (device pointers, asynchronous).  states_out may be NULL.
+ * TRAJ_E_ARG: null state / out, n < 0, B < 0, unknown kind. */
+#define TRAJ_RNG_RAW    0
+#define TRAJ_RNG_DOUBLE 1
+#define TRAJ_RNG_NORMAL 2
+int traj_gen_rng_draw_host(const unsigned long long* state /*[4]*/, int kind, long long n, void* out /*[n]*/,
+                           unsigned long long* state_out /*[4] or NULL*/);
+int traj_gen_rng_draw_batch(int B, int n, int kind, const unsigned long long* states /*[B,4]*/,
+                            void* out /*[B,n]*/, unsigned long long* states_out /*[B,4] or NULL*/,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -93,7 +93,20 @@ class GenConfig(C.Structure):
     ]
 
 
+class FsmRules(C.Structure):
+    """traj_gen_fsm_rules (include/trajgen.h: ControlRules of generation_type2.py:22-30 and the cdfs of the two mode
+    choices of :109-112)."""
+    _fields_ = [
+        ("v_turn_max", C.c_double), ("v_high", C.c_double),
+        ("d_range", C.c_double * 2), ("delta_turn_range", C.c_double * 2),
+        ("delta_straight_noise", C.c_double),
+        ("cdf_after_turn", C.c_double * 2), ("cdf_any", C.c_double * 4),
+    ]
+
+
 GEN_MODEL_MPC, GEN_MODEL_TYPE1, GEN_MODEL_TYPE2 = 0, 1, 2   # TRAJ_GEN_MODEL_*
+FSM_MODES = ("accelerate", "cruise", "turn_left", "turn_right")   # TRAJ_FSM_ACCELERATE .. TRAJ_FSM_TURN_RIGHT
+RNG_RAW, RNG_DOUBLE, RNG_NORMAL = 0, 1, 2                    # TRAJ_RNG_*
 GEN_STAGE_STEPS = 8                                          # TRAJ_GEN_STAGE_STEPS
 GEN_FORM_DEFAULT, GEN_FORM_STAGED, GEN_FORM_DIRECT = 0, 1, 2  # traj_gen_debug_store_form
 GEN_DEFAULT_FORM = GEN_FORM_DIRECT                           # TRAJ_GEN_DEFAULT_FORM
@@ -172,6 +185,11 @@ _SIGS = {
     "traj_gen_simulate_batch": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(GenConfig), C.c_int, C.c_int, _V, _V,
                                           _V, _V, _V]),
     "traj_gen_debug_store_form": (C.c_int, [C.c_int]),
+    "traj_gen_fsm_default_rules": (C.c_int, [C.POINTER(FsmRules)]),
+    "traj_gen_piecewise_batch": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(GenConfig), C.POINTER(FsmRules), C.c_int,
+                                           C.c_int, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_gen_rng_draw_host": (C.c_int, [_V, C.c_int, C.c_longlong, _V, _V]),
+    "traj_gen_rng_draw_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _V, _V, _V, _V]),
     "traj_closed_loop_step": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
                                         _V, _V, _V, C.c_int, C.c_int, _V, _V, _V, _V, _V, C.c_size_t, _V]),
     "traj_closed_loop_run": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
@@ -233,6 +251,12 @@ def default_gen_config(model: int, Ts: float) -> GenConfig:
     c = GenConfig()
     check(lib().traj_gen_default_config(C.byref(c), int(model), float(Ts)), "traj_gen_default_config")
     return c
+
+
+def default_fsm_rules() -> FsmRules:
+    r = FsmRules()
+    check(lib().traj_gen_fsm_default_rules(C.byref(r)), "traj_gen_fsm_default_rules")
+    return r
 
 
 def exported_symbols() -> list[str]:

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GenConfig, MpcConfig, Paths, VehicleParams
+from ._lib import FsmRules, GenConfig, MpcConfig, Paths, VehicleParams
 
 REFERENCE_PARAMS = {
     "Cm1": 0.287, "Cm2": 0.0545, "Cr0": 0.0518, "Cr2": 0.00035,
@@ -184,6 +184,81 @@ def set_gen_store_form(form: int) -> None:
     """Experiments and tests: the kernel form of the following simulate_open_loop calls (_lib.GEN_FORM_DEFAULT /
     GEN_FORM_STAGED / GEN_FORM_DIRECT, traj_gen_debug_store_form).  Results do not depend on it."""
     _lib.check(_lib.lib().traj_gen_debug_store_form(int(form)), "traj_gen_debug_store_form")
+
+
+def fsm_rules_struct(rules=None) -> FsmRules:
+    """traj_gen_fsm_rules from a generation_type2.ControlRules (or anything with its fields; None: the defaults).
+    The two mode distributions of generation_type2.py:109-112 go in as Generator.choice forms them:
+    cdf = p.cumsum() / p.cumsum()[-1]."""
+    if isinstance(rules, FsmRules):
+        return rules
+    r = _lib.default_fsm_rules()
+    if rules is not None:
+        r.v_turn_max, r.v_high = float(rules.v_turn_max), float(rules.v_high)
+        r.delta_straight_noise = float(rules.delta_straight_noise)
+        for i in range(2):
+            r.d_range[i] = float(rules.d_range[i])
+            r.delta_turn_range[i] = float(rules.delta_turn_range[i])
+    for name, p in (("cdf_after_turn", [0.5, 0.5]), ("cdf_any", [0.35, 0.35, 0.15, 0.15])):
+        cdf = np.asarray(p, dtype=np.float64).cumsum()
+        cdf /= cdf[-1]
+        for i, v in enumerate(cdf):
+            getattr(r, name)[i] = float(v)
+    return r
+
+
+def simulate_piecewise(x0, rng_state, T, Ts=0.01, rules=None, params=None, want_rng_state=False) -> dict:
+    """B type-2 trajectories of T steps in one launch (traj_gen_piecewise_batch): the state-machine controller of
+    generation_type2.py:95-157 on each trajectory's own numpy stream, and the Euler loop of :180-187, from x0 [B,6].
+    rng_state [B,4] uint64: np.random.PCG64(seed + i).state as (state >> 64, state & M, inc >> 64, inc & M)
+    (generation_type2.pcg64_states).  Returns torch.cuda tensors X [B,T+1,6], U [B,T,2], mode [B,T] uint8 (codes of
+    _lib.FSM_MODES) and, with want_rng_state, rng_state [B,4] int64 (the bits of the uint64 words) after the last draw."""
+    x0 = _dev(x0, (-1, 6))
+    B, T = x0.shape[0], int(T)
+    st = np.ascontiguousarray(rng_state, dtype=np.uint64)
+    if st.shape != (B, 4):
+        raise ValueError(f"rng_state must be [B,4] uint64 with B = {B}, got {st.shape}")
+    st = torch.from_numpy(st.view(np.int64)).to(x0.device)
+    X = torch.empty((B, T + 1, 6), dtype=torch.float64, device=x0.device)
+    U = torch.empty((B, T, 2), dtype=torch.float64, device=x0.device)
+    mode = torch.empty((B, T), dtype=torch.uint8, device=x0.device)
+    st_out = torch.empty_like(st) if want_rng_state else None
+    cfg = gen_config_struct(_lib.GEN_MODEL_TYPE2, Ts)
+    rc = _lib.lib().traj_gen_piecewise_batch(C.byref(params_struct(params)), C.byref(cfg),
+                                             C.byref(fsm_rules_struct(rules)), B, T, _p(x0), _p(st), _p(X), _p(U),
+                                             _p(mode), _p(st_out), _stream())
+    _lib.check(rc, "traj_gen_piecewise_batch")
+    out = dict(X=X, U=U, mode=mode)
+    if want_rng_state:
+        out["rng_state"] = st_out
+    return out
+
+
+def rng_draw_batch(rng_state, n, kind) -> tuple:
+    """Tests of csrc/gen_rng.h: every one of the B streams rng_state [B,4] uint64 draws n values of `kind`
+    (_lib.RNG_RAW -> uint64, RNG_DOUBLE / RNG_NORMAL -> float64) on the GPU.  Returns (draws [B,n], states [B,4]
+    uint64) as numpy arrays."""
+    dev = require_gpu()
+    st = np.ascontiguousarray(rng_state, dtype=np.uint64)
+    B = st.shape[0]
+    st_d = torch.from_numpy(st.view(np.int64)).to(dev)
+    out = torch.empty((B, int(n)), dtype=torch.int64, device=dev)
+    st_out = torch.empty_like(st_d)
+    _lib.check(_lib.lib().traj_gen_rng_draw_batch(B, int(n), int(kind), _p(st_d), _p(out), _p(st_out), _stream()),
+               "traj_gen_rng_draw_batch")
+    h = out.cpu().numpy()
+    return (h.view(np.uint64) if kind == _lib.RNG_RAW else h.view(np.float64)), st_out.cpu().numpy().view(np.uint64)
+
+
+def rng_draw_host(state, n, kind) -> tuple:
+    """The same header on the CPU (traj_gen_rng_draw_host): n draws from one stream state [4] uint64."""
+    st = np.ascontiguousarray(state, dtype=np.uint64).reshape(4)
+    out = np.empty(int(n), dtype=np.uint64 if kind == _lib.RNG_RAW else np.float64)
+    st_out = np.empty(4, dtype=np.uint64)
+    _lib.check(_lib.lib().traj_gen_rng_draw_host(C.c_void_p(st.ctypes.data), int(kind), int(n),
+                                                 C.c_void_p(out.ctypes.data), C.c_void_p(st_out.ctypes.data)),
+               "traj_gen_rng_draw_host")
+    return out, st_out
 
 
 # ---------------------------------------------------------------- MPC step

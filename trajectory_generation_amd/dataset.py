@@ -209,6 +209,33 @@ def generate_open_loop(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shard
     return X, U
 
 
+def generate_piecewise(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shards=False):
+    """The reference's second dataset (generation_traj/generation_type2.py:162-220, :290-322), B trajectories of T
+    steps per rank: this rank's ids rank * B .. rank * B + B - 1 of the dataset seeded with `seed`
+    (generation_type2.generate_steps: the controller, its random streams and the simulation in one kernel launch),
+    gathered to rank 0, which writes ``{out_prefix}_clean.csv`` / ``{out_prefix}_noisy.csv`` (write_csv: the
+    reference's noise seeds 12345 + id, sigmas and columns; mode strings are not written, the reference drops them).
+    shards: no gather, every rank writes ``{out_prefix}_rank{r}_*.csv`` with its global ids.
+    Returns (X [W B,T+1,6], U [W B,T,2]) on rank 0 and None on the other ranks (shards: this rank's share)."""
+    import torch
+    from .generation_type2 import generate_steps
+    rank = dist.get_rank() if (dist is not None and dist.is_initialized()) else 0
+    res = generate_steps(B, T, Ts, seed=seed, id_offset=rank * B)
+    X, U = res["X"], res["U"]
+    if shards:
+        if out_prefix is not None:
+            write_csv(f"{out_prefix}_rank{rank}", X.cpu().numpy(), U.cpu().numpy(), res["ids"], Ts)
+        return X, U
+    status = torch.zeros((T, B), dtype=torch.int32, device=X.device)
+    blk = gather_to_root(pack_history(X, U, status), dist)
+    if blk is None:
+        return None
+    X, U, _ = unpack_history(blk)
+    if out_prefix is not None:
+        write_csv(out_prefix, X.cpu().numpy(), U.cpu().numpy(), np.arange(X.shape[0]), Ts)
+    return X, U
+
+
 def merge_datasets(first_prefix, second_prefix, out_prefix):
     """generation_traj/merge_datasets.py:33-70 for ``{prefix}_clean.csv`` / ``{prefix}_noisy.csv`` pairs: the second
     pair's trajectory ids are shifted by id_offset = max(trajectory_id of the first clean file) + 1 and appended to

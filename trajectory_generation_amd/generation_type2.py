@@ -1,0 +1,216 @@
+"""Import swap for the reference's generation_traj/generation_type2.py (the piecewise state-machine generator).
+
+``import trajectory_generation_amd.generation_type2 as generation_type2`` provides the reference module's names with
+its signatures -- Params, ControlRules, clamp, tire_forces, f_cont, euler_step, sample_controls_piecewise -- and a
+batched generate_dataset in place of its per-trajectory loop (:162-220): ONE kernel launch
+(batch.simulate_piecewise, include/trajgen.h traj_gen_piecewise_batch) runs the controller, its random stream and the
+Euler integration of all trajectories on the GPU, one lane per trajectory.  Plotting and animation are left out.
+
+The single-trajectory functions run on the host in numpy with np.random.default_rng; they are the specification the
+kernel is tested against.  Nothing sequential is left on the host: every trajectory has a stream of its own
+(default_rng(seed + i)), whose PCG64 state the kernel takes over (pcg64_states), and the one shared stream, the x0
+draw from default_rng(seed), takes exactly six uniforms per trajectory, so a shard jumps to its place in it
+(draw_x0: PCG64.advance, nothing drawn and discarded).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, Tuple
+
+import numpy as np
+
+Params = {
+    "Cm1": 0.287, "Cm2": 0.0545, "Cr0": 0.0518, "Cr2": 0.00035,
+    "Br": 3.3852, "Cr": 1.2691, "Dr": 0.1737, "Bf": 2.579,
+    "Cf": 1.2, "Df": 0.192, "m": 0.041, "Iz": 27.8e-6,
+    "lf": 0.029, "lr": 0.033, "g": 9.81, "maxAlpha": 0.6, "vx_zero": 0.3,
+}
+
+X0_RANGES = ((-2, 2), (-2, 2), (-np.pi, np.pi), (0.2, 0.6), (-0.05, 0.05), (-1, 1))   # :171-174
+MODES = ("accelerate", "cruise", "turn_left", "turn_right")    # the kernel's mode codes 0 .. 3 (_lib.FSM_MODES)
+
+
+@dataclass
+class ControlRules:
+    """generation_type2.py:21-43."""
+    v_turn_max: float = 1.2
+    v_high: float = 4.0
+    d_range: Tuple[float, float] = (0.0, 0.33)
+    delta_turn_range: Tuple[float, float] = (0.015, 0.04)
+    delta_straight_noise: float = 0.004
+    d_noise_std: float = 0.008
+    delta_noise_std: float = 0.002
+    meas_noise_std: Dict[str, float] = None
+
+    def __post_init__(self):
+        if self.meas_noise_std is None:
+            from .dataset import MEAS_NOISE_STD
+            self.meas_noise_std = dict(MEAS_NOISE_STD)
+
+
+def clamp(x, lo, hi):
+    return np.minimum(np.maximum(x, lo), hi)
+
+
+def tire_forces(x, u, p):
+    """(Fy_f, Fy_r, Frx) of generation_type2.py:52-71: generation_type1's forces (vx_eff = max(|vx|, vx_zero) without
+    a sign, also in Frx) with the rear slip angle clamped like the front one."""
+    vx, vy, omega = x[3], x[4], x[5]
+    d, delta = u
+    lim = p["maxAlpha"]
+    vx_eff = max(abs(vx), p["vx_zero"])
+    slip = {"f": clamp(-np.arctan2(omega * p["lf"] + vy, vx_eff) + delta, -lim, lim),
+            "r": clamp(np.arctan2(omega * p["lr"] - vy, vx_eff), -lim, lim)}
+    Fy = {a: p["D" + a] * np.sin(p["C" + a] * np.arctan(p["B" + a] * slip[a])) for a in ("f", "r")}   # Pacejka
+    Frx = (p["Cm1"] - p["Cm2"] * vx_eff) * d - p["Cr0"] - p["Cr2"] * (vx_eff ** 2)
+    return Fy["f"], Fy["r"], Frx
+
+
+def f_cont(x, u, p):
+    """State derivative of the dynamic bicycle model, generation_type2.py:73-86 (divides by m and Iz)."""
+    phi, vx, vy, omega = x[2], x[3], x[4], x[5]
+    delta = u[1]
+    Fy_f, Fy_r, Frx = tire_forces(x, u, p)
+    m = p["m"]
+    return np.array([
+        vx * np.cos(phi) - vy * np.sin(phi),
+        vx * np.sin(phi) + vy * np.cos(phi),
+        omega,
+        (Frx - Fy_f * np.sin(delta) + m * vy * omega) / m,
+        (Fy_r + Fy_f * np.cos(delta) - m * vx * omega) / m,
+        (Fy_f * p["lf"] * np.cos(delta) - Fy_r * p["lr"]) / p["Iz"],
+    ])
+
+
+def euler_step(x, u, p, Ts):
+    return x + Ts * f_cont(x, u, p)
+
+
+# the controller's constants (generation_type2.py:97, :101, :114, :131-133); include/trajgen.h TRAJ_FSM_*
+DELTA_RATE_MAX, V_FLOOR, D_BOOST_MIN, V_STALL, STALL_SEG_S, SEG_S = 0.30, 0.35, 0.15, 0.5, 0.3, (0.4, 1.5)
+STRAIGHT, ANY = ("accelerate", "cruise"), MODES
+P_STRAIGHT, P_ANY = (0.5, 0.5), (0.35, 0.35, 0.15, 0.15)
+
+
+def _start_segment(rng, rules, v, after_turn, Ts):
+    """One segment start (generation_type2.py:107-133) at speed v: (label, d, delta, steps).  The draws come in the
+    reference's order -- mode, length, the mode's throttle and steering, then the stall override's two."""
+    names, p = (STRAIGHT, P_STRAIGHT) if after_turn else (ANY, P_ANY)
+    label = str(rng.choice(list(names), p=list(p)))
+    steps = max(1, int(np.round(rng.uniform(*SEG_S) / Ts)))
+    noise = rules.delta_straight_noise
+    if label in STRAIGHT:
+        lo, hi = (0.3, rules.d_range[1]) if label == "accelerate" else (-0.05, 0.2)
+        if label == "accelerate" and v >= rules.v_high:
+            label = "cruise"                       # the label only: the accelerate draws stay
+        d = rng.uniform(lo, hi)
+        delta = rng.normal(0.0, noise)
+    else:
+        d = rng.uniform(0.0, 0.15) if v > rules.v_turn_max else rng.uniform(0.05, 0.25)
+        mag = rng.uniform(*rules.delta_turn_range)
+        shrink = min(1.0, rules.v_turn_max / max(v, 1e-3))
+        delta = (mag if label == "turn_left" else -mag) * shrink
+    if v < V_STALL:
+        label = "accelerate"
+        d = rng.uniform(0.5, 1.0)
+        delta = rng.normal(0.0, noise)
+        steps = max(steps, int(round(STALL_SEG_S / Ts)))
+    return label, d, delta, steps
+
+
+def sample_controls_piecewise(sim_steps, Ts, x0, p, rules: ControlRules, seed=42, rng=None):
+    """generation_type2.py:95-157: (U [sim_steps,2], modes [sim_steps] of str).  A random driving mode per segment
+    of uniform(0.4, 1.5) seconds, its throttle and steering drawn per mode and adjusted by the speed of a shadow
+    simulation (relabel at v_high, slower turns above v_turn_max, stall override below 0.5, throttle boost below
+    0.35), the steering rate-limited to 0.30 rad/s.  rng (not in the reference): a Generator to draw from instead of
+    default_rng(seed) -- the tests read its state afterwards."""
+    rng = np.random.default_rng(seed) if rng is None else rng
+    U = np.zeros((sim_steps, 2))
+    modes = [""] * sim_steps
+    shadow = np.array(x0, dtype=float)
+    last_delta, after_turn, k = 0.0, False, 0
+    while k < sim_steps:
+        label, d, delta, steps = _start_segment(rng, rules, np.hypot(shadow[3], shadow[4]), after_turn, Ts)
+        for k in range(k, min(sim_steps, k + steps)):
+            if np.hypot(shadow[3], shadow[4]) < V_FLOOR:
+                d = max(d, D_BOOST_MIN)            # persists for the rest of the segment
+            reach = DELTA_RATE_MAX * Ts
+            want = float(np.clip(delta, -0.6, 0.6))
+            last_delta = float(np.clip(want, last_delta - reach, last_delta + reach))
+            U[k] = float(np.clip(d, *rules.d_range)), last_delta
+            modes[k] = label
+            shadow = euler_step(shadow, U[k], p, Ts)
+            shadow[3] = max(shadow[3], 0.0)
+            shadow[5] = float(np.clip(shadow[5], -6, 6))
+        k += 1
+        after_turn = label.startswith("turn")
+    return U, modes
+
+
+def simulate_trajectory(x0, U_sim, Ts, p):
+    """The ground-truth loop of generation_type2.py:180-187 (not a name of the reference, which has it inline):
+    explicit Euler, vx floored at 0 and omega clipped to +-6 in the stored state.  Returns [T+1,6]."""
+    T = len(U_sim)
+    X = np.empty((T + 1, 6))
+    X[0] = x0
+    for k in range(T):
+        X[k + 1] = X[k] + Ts * f_cont(X[k], U_sim[k], p)
+        X[k + 1, 3] = max(X[k + 1, 3], 0.0)
+        X[k + 1, 5] = float(np.clip(X[k + 1, 5], -6, 6))
+    return X
+
+
+# ---------------------------------------------------------------- the batched generate_dataset
+
+def draw_x0(num_traj, seed=2025, id_offset=0):
+    """x0 [num_traj,6] of trajectories id_offset .. id_offset + num_traj - 1 (generation_type2.py:164, :171-174):
+    six uniforms each from default_rng(seed), the stream advanced by 6 id_offset draws (PCG64.advance)."""
+    bg = np.random.PCG64(seed)
+    if id_offset:
+        bg.advance(6 * int(id_offset))
+    rng = np.random.Generator(bg)
+    x0 = np.empty((num_traj, 6))
+    for i in range(num_traj):
+        for j, (lo, hi) in enumerate(X0_RANGES):
+            x0[i, j] = rng.uniform(lo, hi)
+    return x0
+
+
+def pcg64_state_words(bit_generator):
+    """A PCG64's state as the kernel takes it: uint64 (state >> 64, state & M, inc >> 64, inc & M), M = 2^64 - 1."""
+    s = bit_generator.state["state"]
+    m = (1 << 64) - 1
+    return np.array([s["state"] >> 64, s["state"] & m, s["inc"] >> 64, s["inc"] & m], dtype=np.uint64)
+
+
+def pcg64_states(seeds):
+    """[n,4] uint64: the states of np.random.default_rng(s) for s in seeds (SeedSequence runs here, on the host)."""
+    return np.array([pcg64_state_words(np.random.PCG64(int(s))) for s in seeds], dtype=np.uint64).reshape(-1, 4)
+
+
+def generate_steps(num_traj, steps, Ts=0.01, seed=2025, id_offset=0, rules=None, device=None, want_rng_state=False):
+    """generate_dataset with the length given in steps."""
+    import torch
+
+    from . import batch as TB
+    dev = TB.require_gpu(device)
+    ids = np.arange(id_offset, id_offset + num_traj)
+    x0 = draw_x0(num_traj, seed, id_offset)
+    states = pcg64_states(seed + ids)
+    with torch.cuda.device(dev):
+        out = TB.simulate_piecewise(torch.as_tensor(x0, device=dev), states, steps, Ts, rules, Params,
+                                    want_rng_state=want_rng_state)
+    res = {"X": out["X"], "U": out["U"], "modes": out["mode"], "ids": ids}
+    if want_rng_state:
+        res["rng_state"] = out["rng_state"]
+    return res
+
+
+def generate_dataset(num_traj, T, Ts, seed=2025, id_offset=0, rules=None, device=None):
+    """The reference's generate_dataset (generation_type2.py:162-220; T in seconds, int(np.round(T / Ts)) steps) for
+    trajectories id_offset .. id_offset + num_traj - 1 of the dataset seeded with `seed`, in one kernel launch.
+
+    Returns {"X": [n,steps+1,6], "U": [n,steps,2], "modes": [n,steps] uint8} (torch tensors on the GPU; mode codes
+    index MODES) and "ids" (numpy).  Measurement noise is added when the files are written (dataset.write_csv draws it
+    per id from default_rng(12345 + id), as the reference does at :189-200)."""
+    return generate_steps(num_traj, int(np.round(T / Ts)), Ts, seed, id_offset, rules, device)
