@@ -11,6 +11,11 @@ VehicleModel.f from random initial states and random controls, observed through 
 A second set, knet_b37_t60_im10.npz, covers a ragged batch (B=37, not a multiple of the 4 sequences a fused
 workgroup owns), a longer recurrence (T=60) and the in_mult 10 architecture (training.py / test_prediction.py,
 FC5 60 wide) with weight seed 2.
+
+A third set, knet_b9_t12_unorm.npz (B=9, T=12, in_mult 5, weight seed 3), runs the module with control
+normalization: set_normalization(..., u_mean, u_std) of shape [1, 2, 1] computed from the simulated controls, and
+normalized controls fed to forward (kalman_net.py:12-25, :138-149).  Its ``u`` is what the module is fed (the
+normalized controls); ``u_real``, ``u_mean`` and ``u_std`` are stored beside it.
 """
 import os
 import sys
@@ -26,7 +31,7 @@ from tests._knet_weights import LIMITS, knet_weights  # noqa: E402
 REF = "/root/reference/KalmanNet"
 
 
-def main(B=4, T=20, in_mult=5, wseed=0, rseed=7, fname="knet.npz"):
+def main(B=4, T=20, in_mult=5, wseed=0, rseed=7, fname="knet.npz", unorm=False):
     sys.path.insert(0, REF)
     import kalman_net as KN
     import vehicle_model as VM
@@ -69,7 +74,16 @@ def main(B=4, T=20, in_mult=5, wseed=0, rseed=7, fname="knet.npz"):
 
     model = KN.KalmanNetNN()
     model.NNBuild(sysm, in_mult_KNet=in_mult, out_mult_KNet=40, hidden_dim_gru=128)
-    model.set_normalization(f32(x_mean), f32(x_std), f32(y_mean), f32(y_std))
+    extra = {}
+    U_in = U                         # what forward() is fed
+    if unorm:
+        u_mean = U.mean(axis=(0, 2)).reshape(1, 2, 1)
+        u_std = U.std(axis=(0, 2)).reshape(1, 2, 1) + 1e-3
+        U_in = (U - u_mean) / u_std
+        model.set_normalization(f32(x_mean), f32(x_std), f32(y_mean), f32(y_std), f32(u_mean), f32(u_std))
+        extra = {"u_mean": u_mean, "u_std": u_std, "u_real": U}
+    else:
+        model.set_normalization(f32(x_mean), f32(x_std), f32(y_mean), f32(y_std))
     sd = {k: torch.tensor(v) for k, v in knet_weights(seed=wseed, in_mult=in_mult).items()}
     model.load_state_dict(sd)
     model.eval()
@@ -81,7 +95,7 @@ def main(B=4, T=20, in_mult=5, wseed=0, rseed=7, fname="knet.npz"):
         model.init_hidden_KNet()
         model.InitSequence(f32(m1x0), T)
         for t in range(T):
-            xo = model(f32(y_norm[:, :, t:t + 1]), f32(U[:, :, t:t + 1]))
+            xo = model(f32(y_norm[:, :, t:t + 1]), f32(U_in[:, :, t:t + 1]))
             post.append(xo.squeeze(2).numpy())
             prior.append(model.m1x_prior.squeeze(2).numpy())
             kg.append(model.KGain.numpy())
@@ -89,13 +103,15 @@ def main(B=4, T=20, in_mult=5, wseed=0, rseed=7, fname="knet.npz"):
         os.path.join(HERE, fname), Ts=Ts, seed=wseed, in_mult=in_mult, out_mult=40, hidden=128,
         limits=np.array([LIMITS[k] for k in sorted(LIMITS)]), limit_names=np.array(sorted(LIMITS)),
         phys_x=xp, phys_u=up, pt_f_cont=f_cont, f_step=f_step,
-        x_mean=x_mean, x_std=x_std, y_mean=y_mean, y_std=y_std, y_norm=y_norm, u=U, x_true=X, m1x0=m1x0,
-        x_post=np.stack(post, 2), x_prior=np.stack(prior, 2), KG=np.stack(kg, 3))
+        x_mean=x_mean, x_std=x_std, y_mean=y_mean, y_std=y_std, y_norm=y_norm, u=U_in, x_true=X, m1x0=m1x0,
+        x_post=np.stack(post, 2), x_prior=np.stack(prior, 2), KG=np.stack(kg, 3), **extra)
     print("wrote", fname, np.stack(post, 2).shape)
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "b37":
         main(B=37, T=60, in_mult=10, wseed=2, rseed=23, fname="knet_b37_t60_im10.npz")
+    elif len(sys.argv) > 1 and sys.argv[1] == "unorm":
+        main(B=9, T=12, in_mult=5, wseed=3, rseed=41, fname="knet_b9_t12_unorm.npz", unorm=True)
     else:
         main()

@@ -12,14 +12,18 @@ pytestmark = pytest.mark.gpu
 G = np.load("tests/golden/knet.npz")
 
 
-def build(dev, seed=0, in_mult=5, g=G):
+def build(dev, seed=0, in_mult=5, g=G, u_stats=None):
+    """u_stats: (u_mean, u_std) for control normalization; by default those of g when it carries them."""
     from trajectory_generation_amd import knet as K
     sysm = K.VehicleModel(float(g["Ts"]), 20, 20, torch.zeros(6, 1))
     sysm.Params.update(LIMITS)
     model = K.KalmanNetNN(dev)
     model.NNBuild(sysm, in_mult_KNet=in_mult, out_mult_KNet=40, hidden_dim_gru=128)
     f32 = lambda a: torch.tensor(a, dtype=torch.float32)   # noqa: E731
-    model.set_normalization(f32(g["x_mean"]), f32(g["x_std"]), f32(g["y_mean"]), f32(g["y_std"]))
+    if u_stats is None and "u_mean" in g.files:
+        u_stats = (g["u_mean"], g["u_std"])
+    model.set_normalization(f32(g["x_mean"]), f32(g["x_std"]), f32(g["y_mean"]), f32(g["y_std"]),
+                            *([f32(a) for a in u_stats] if u_stats is not None else []))
     sd = {k: torch.tensor(v) for k, v in knet_weights(seed=seed, in_mult=in_mult).items()}
     model.load_state_dict(sd, strict=True)
     model.eval()
@@ -49,7 +53,10 @@ def test_missing_limits_raise_like_reference(gpu):
         sysm.f(x, u)
 
 
-@pytest.mark.parametrize("name", ["knet.npz", "knet_b37_t60_im10.npz"])
+GOLDENS = ["knet.npz", "knet_b37_t60_im10.npz", "knet_b9_t12_unorm.npz"]
+
+
+@pytest.mark.parametrize("name", GOLDENS)
 def test_sequence_vs_reference(gpu, name):
     g = np.load("tests/golden/" + name)
     _, _, model = build(gpu, seed=int(g["seed"]), in_mult=int(g["in_mult"]), g=g)
@@ -98,21 +105,31 @@ def test_graph_runner_matches_eager_and_oracle(gpu):
     assert np.abs(eager - ref).max() <= 2e-4 * (1 + np.abs(ref).max())
 
 
-@pytest.mark.parametrize("B,T,groups,in_mult", [(64, 30, 1, 5), (7, 5, 1, 5), (1, 3, 1, 5), (37, 6, 3, 5),
-                                                 (64, 30, 1, 10), (37, 6, 3, 10)])
-def test_fused_runner_vs_oracle(gpu, B, T, groups, in_mult):
+@pytest.mark.parametrize("B,T,groups,in_mult,unorm", [
+    pytest.param(64, 30, 1, 5, False, id="64-30-1-5"), pytest.param(7, 5, 1, 5, False, id="7-5-1-5"),
+    pytest.param(1, 3, 1, 5, False, id="1-3-1-5"), pytest.param(37, 6, 3, 5, False, id="37-6-3-5"),
+    pytest.param(64, 30, 1, 10, False, id="64-30-1-10"), pytest.param(37, 6, 3, 10, False, id="37-6-3-10"),
+    pytest.param(37, 6, 3, 5, True, id="37-6-3-5-unorm")])
+def test_fused_runner_vs_oracle(gpu, B, T, groups, in_mult, unorm):
     """Fused step (traj_knet_front_f32 / FC2 GEMMs / traj_knet_back_f32, whole-T graph) vs the CPU oracle,
     ragged batches (B not a multiple of the 4 sequences a workgroup owns) included, for the reference's two
     architectures (in_mult 5: test_vehicle.py / training_prediction.py; 10: training.py / test_prediction.py,
-    FC5 60 wide)."""
+    FC5 60 wide).  unorm: with control statistics set (u_mean / u_std of knet_b9_t12_unorm.npz, normalized controls
+    fed), against the float64 reference of tests/_knet_ref.py (the oracle has no control normalization)."""
     from oracle import knet_oracle as KO
+    from tests import _knet_ref as R
     from trajectory_generation_amd.knet import KNetSequenceRunner
-    _, sysm, model = build(gpu, seed=1, in_mult=in_mult)
+    gu = np.load("tests/golden/knet_b9_t12_unorm.npz")
+    u_stats = (gu["u_mean"], gu["u_std"]) if unorm else None
+    _, sysm, model = build(gpu, seed=1, in_mult=in_mult, u_stats=u_stats)
+    assert model.has_norm_params_u == unorm
     rng = np.random.default_rng(11 + B)
     y = torch.tensor(rng.normal(size=(B, 5, T)), dtype=torch.float32, device=gpu)
     u = torch.tensor(np.stack([rng.uniform(0, 0.5, (B, T)), rng.uniform(-0.3, 0.3, (B, T))], 1), dtype=torch.float32,
                      device=gpu)
     m1x0 = torch.tensor(rng.normal(size=(B, 6, 1)) * 0.5, dtype=torch.float32, device=gpu)
+    if unorm:   # the same real controls, fed normalized
+        u = ((u - model.u_mean.reshape(1, 2, 1)) / model.u_std.reshape(1, 2, 1)).contiguous()
     run = KNetSequenceRunner(model, B, groups=groups)
     eager = run.run(y, u, m1x0, use_graph=False).cpu().numpy()
     f0 = run.run(y, u, m1x0, use_graph=False, fused=True).cpu().numpy()
@@ -125,17 +142,24 @@ def test_fused_runner_vs_oracle(gpu, B, T, groups, in_mult):
     np.testing.assert_array_equal(fs, f0)
     p = dict(KO.PARAMS)
     p.update(LIMITS)
-    ref = KO.run_sequences(knet_weights(1, in_mult=in_mult), p, float(G["Ts"]), y.cpu().numpy(), u.cpu().numpy(),
-                           m1x0.cpu().numpy(), G["x_mean"], G["x_std"], G["y_mean"], G["y_std"]).numpy()
+    if unorm:
+        xm, xs, ym, ys = model._norm_tensors()
+        ref = R.run64(knet_weights(1, in_mult=in_mult), p, float(G["Ts"]), y, u, m1x0, xm, xs, ym, ys, model.u_mean,
+                      model.u_std)[0].numpy()
+    else:
+        ref = KO.run_sequences(knet_weights(1, in_mult=in_mult), p, float(G["Ts"]), y.cpu().numpy(),
+                               u.cpu().numpy(), m1x0.cpu().numpy(), G["x_mean"], G["x_std"], G["y_mean"],
+                               G["y_std"]).numpy()
     t = 2e-4 * (1 + np.abs(ref).max())
     assert np.abs(f0 - ref).max() <= t
     assert np.abs(f0 - eager).max() <= t
 
 
-@pytest.mark.parametrize("name", ["knet.npz", "knet_b37_t60_im10.npz"])
+@pytest.mark.parametrize("name", GOLDENS)
 def test_fused_runner_vs_reference_goldens(gpu, name):
-    """The fused whole-T graph against the reference module's posteriors: B=4 x T=20 (in_mult 5) and a ragged
-    B=37 x T=60 batch of the in_mult 10 architecture (tests/golden/gen_knet_golden.py)."""
+    """The fused whole-T graph against the reference module's posteriors: B=4 x T=20 (in_mult 5), a ragged
+    B=37 x T=60 batch of the in_mult 10 architecture, and B=9 x T=12 with control normalization (u_mean / u_std set,
+    normalized controls fed) (tests/golden/gen_knet_golden.py)."""
     from trajectory_generation_amd.knet import KNetSequenceRunner
     g = np.load("tests/golden/" + name)
     _, _, model = build(gpu, seed=int(g["seed"]), in_mult=int(g["in_mult"]), g=g)
