@@ -274,6 +274,13 @@ __device__ __forceinline__ double fma3(double a, double b, double c) {
     return r;
 }
 
+// fma3(-a, b, c) with the negation as the instruction's source modifier (no separate sign flip of a)
+__device__ __forceinline__ double fma3n(double a, double b, double c) {
+    double r;
+    asm("v_fma_f64 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
 // Read NN (even) doubles from a 16-byte aligned LDS buffer as NN/2 ds_read_b128, all issued before
 // the first use (the default schedule waits on each read in turn under register pressure).
 template <int NN>
@@ -286,6 +293,33 @@ __device__ __forceinline__ void lds_load_all(const double* p, double (&o)[NN]) {
         o[2 * i + 1] = v.y;
     }
     __builtin_amdgcn_sched_group_barrier(0x100, NN / 2, 0);
+}
+
+// Ten ds_read_b128 from the LDS byte address a + OFF into r[0..9] on the lanes of the mask m ONLY: the other lanes keep
+// their r.  (Written as a conditional the same reads make r a phi of two values, and a row of 40 doubles filled under
+// five different conditions then costs copies of itself and spills.)  The reads complete before the statement ends.
+typedef double v2d_t __attribute__((ext_vector_type(2)));
+template <int OFF>
+__device__ __forceinline__ void lds_load10_masked(unsigned a, unsigned long long m, v2d_t* r) {
+    unsigned long long sv;
+    asm volatile(
+        "s_mov_b64 %[sv], exec\n\t"
+        "s_and_b64 exec, exec, %[m]\n\t"
+        "ds_read_b128 %[r0], %[a] offset:%[o0]\n\t"
+        "ds_read_b128 %[r1], %[a] offset:%[o1]\n\t"
+        "ds_read_b128 %[r2], %[a] offset:%[o2]\n\t"
+        "ds_read_b128 %[r3], %[a] offset:%[o3]\n\t"
+        "ds_read_b128 %[r4], %[a] offset:%[o4]\n\t"
+        "ds_read_b128 %[r5], %[a] offset:%[o5]\n\t"
+        "ds_read_b128 %[r6], %[a] offset:%[o6]\n\t"
+        "ds_read_b128 %[r7], %[a] offset:%[o7]\n\t"
+        "ds_read_b128 %[r8], %[a] offset:%[o8]\n\t"
+        "ds_read_b128 %[r9], %[a] offset:%[o9]\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(sv), [r0] "+v"(r[0]), [r1] "+v"(r[1]), [r2] "+v"(r[2]), [r3] "+v"(r[3]), [r4] "+v"(r[4]), [r5] "+v"(r[5]), [r6] "+v"(r[6]), [r7] "+v"(r[7]), [r8] "+v"(r[8]), [r9] "+v"(r[9])
+        : [a] "v"(a), [m] "s"(m), [o0] "i"(OFF + 0), [o1] "i"(OFF + 16), [o2] "i"(OFF + 32), [o3] "i"(OFF + 48), [o4] "i"(OFF + 64), [o5] "i"(OFF + 80), [o6] "i"(OFF + 96), [o7] "i"(OFF + 112), [o8] "i"(OFF + 128), [o9] "i"(OFF + 144)
+        : "memory");
 }
 
 // ---- DPP cross-lane moves (gfx9 data-parallel primitives: VALU, no LDS traffic) -------------

@@ -74,6 +74,9 @@
                                // Round 6: all 133 GPU tests green with it, but 200 steps 16.0 M against 16.1 M single
                                // (20 steps within noise, +20 B/lane scratch): off -- same instructions per pivot
 #endif
+#ifndef TGMPC_SWEEP_2D
+#define TGMPC_SWEEP_2D 1       // fused capacity-40 instance at 2 waves per SIMD: K^-1 swept as 8 x 8 blocks of (NN/8)^2 entries, one
+#endif                         // block per lane, all 64 lanes busy (0: the row-per-lane receiver sweep); same values bit for bit
 #ifndef TGMPC_PAIR_CH
 #define TGMPC_PAIR_CH 4        // one-wave pair sweep: pivot-row entries (double2 of the two rows) per chunk
 #endif
@@ -183,6 +186,12 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // FULLP row stride PS = NN + 2 doubles (2 PS = 4 mod 8 dwords): a row-per-lane 16-byte read puts 16 consecutive
     // lanes on 16 distinct 4-bank groups (stride NN = 40 maps every 4th lane to the same banks: 16-way conflicts)
     constexpr int PS = FULLP ? NN + TGMPC_PSPAD : NN;
+    // SW2D: the factorization sweep over an 8 x 8 grid of lanes, each holding a BSW x BSW block of K (see the sweep).
+    // The fused capacity-40 instance at two waves per SIMD; the 3-wave, lean, pair-sweep, per-step and other
+    // capacities' instances keep the row-per-lane sweep (identical arithmetic: they cross-check this one).
+    constexpr bool SW2D = TGMPC_SWEEP_2D && !TGMPC_SWEEP_PAIR && CMP && !LEAN && FULLP && NN == 40;
+    constexpr int BSW = NN / 8;
+    constexpr int ST2 = NN + 2;   // SW2D: row stride of the staging area that turns blocks back into rows
     static_assert(!FULLP || TGMPC_PSPAD != 2 || (2 * PS) % 8 == 4, "conflict-free row stride");
     constexpr int NP = FULLP ? NN * PS : NP0;
     // cumulative Ruiz scaling (the scaling pass) up to capacity 40; the N = 40 problems (condition ~1e9) keep OSQP's
@@ -232,7 +241,9 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     constexpr int NSTR = (CMP && LEAN) ? TGMPC_NSTASH : 5;
     constexpr int NSTASH = LEAN ? ((NSW + 1) & ~1) + NSTR * NN : 0;
     constexpr int NU0 = CMP ? ((NSCR0 > NSCR1) ? NSCR0 : NSCR1) : (L2W ? NSCR0 : NEX + NSW);
-    constexpr int NU = NU0 > NSTASH ? NU0 : NSTASH;
+    constexpr int NU1 = NU0 > NSTASH ? NU0 : NSTASH;
+    // SW2D: 8 staged rows of K^-1 (one local block row of every lane) in the region the sweep leaves dead
+    constexpr int NU = (SW2D && 8 * ST2 > NU1) ? 8 * ST2 : NU1;
     __shared__ __attribute__((aligned(16))) double s_u[NU];
     double* const s_ex = s_u;                     // exchange / broadcast buffers
     double* const s_sw = (CMP || L2W) ? s_u : s_u + NEX;   // sweep pivot columns (16-byte aligned: NEX is even)
@@ -1147,6 +1158,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             return own ? ((sa[0] + sa[1]) + (sa[2] + sa[3])) + ((sa[4] + sa[5]) + (sa[6] + sa[7])) : 0.0;
         };
         double Krow[NN];
+        double Kb[SW2D ? BSW * BSW : 1];   // SW2D: the lane's block of K during the factorization, row-major
         auto Kmul = [&](double v, int slot = -1) -> double {  // (K^{-1} v)_t, KC independent FMA chains
             // (4 at capacity <= 64 -- round 2 chose 4: one wave issues an f64 op about every 8 cycles, 8 chains
             // measured far slower in the fused instance; TGMPC_KMC80 at capacity 80, default 4)
@@ -1417,7 +1429,15 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                     }
                 }
                 __syncthreads();
-                if constexpr (RECV2) {
+                if constexpr (SW2D) {
+                    // lane 8 g + s holds K[BSW g + k][BSW s + l] (padding rows and columns: the identity, from s_P)
+                    const double* const blk = s_P + (BSW * (tt >> 3)) * PS + BSW * (tt & 7);
+#pragma unroll
+                    for (int k = 0; k < BSW; ++k) {
+#pragma unroll
+                        for (int l = 0; l < BSW; ++l) Kb[k * BSW + l] = blk[k * PS + l];
+                    }
+                } else if constexpr (RECV2) {
                     // two-wave receiver sweep: lane t holds row t - SP2 (lanes < SP2: exact zero rows)
                     const int r = tt - SP2;
                     const int rr = r >= 0 ? r : 0;
@@ -1457,7 +1477,128 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
 #if TGMPC_PRIO_SWEEP
             if (FUSED) __builtin_amdgcn_s_setprio(2);   // the sweep's pivot chain is LDS-latency bound
 #endif
-            if constexpr (WAVES == 1 && NN <= 42 && TGMPC_SWEEP_PAIR) {
+            if constexpr (SW2D) {
+                // One-wave sweep with K held as 8 x 8 blocks: lane 8 g + s holds the BSW x BSW block of rows
+                // BSW g .. and columns BSW s .., so all 64 lanes carry data (the row form below: NN of 64) and a
+                // lane reads 2 BSW + 1 values per pivot instead of a whole pivot row.  The arithmetic is the row
+                // form's, entry by entry: with c = column p as published by the lanes that hold it (c_r = K_rp, used
+                // as the pivot column AND, by symmetry, as the pivot row -- K is not bitwise symmetric during the
+                // sweep, and the row form never reads the true row), dinv = rcp_nr(c_p):
+                //     K_ij <- fma3(-(c_i dinv), c_j, K_ij)   (i, j != p; the sign flip is exact wherever it is applied)
+                //     K_pj <- fma3(dinv, c_j, +0.0)          (the row form's receiver lane: an exact zero row)
+                //     K_ip <- c_i dinv,   K_pp <- -dinv.
+                // The lanes holding column p + 1 form it first and publish it (two alternating slots; one wave's LDS
+                // operations complete in program order).  The pivot loop is unrolled over whole blocks of BSW pivots,
+                // so the local row / column p % BSW is a static register: no rotation.  Afterwards the blocks go back
+                // to rows through LDS (below).
+                const int tq = opaque_t();
+                const int g = tq >> 3, s = tq & 7;
+                if (s == 0) {
+#pragma unroll
+                    for (int k = 0; k < BSW; ++k) s_sw[BSW * g + k] = Kb[k * BSW];
+                }
+                __syncthreads();
+                // Two blocks of pivots per loop body (2 BSW pivots: the slot of a pivot is static), and the next
+                // pivot's reads issued right after its column is published, ahead of this pivot's other FMAs (the
+                // reads after the last pivot fetch words nobody uses).
+                const double* const cgp = s_sw + BSW * g;
+                const double* const csp = s_sw + BSW * s;
+                double cg[BSW], cs[BSW];
+#pragma unroll
+                for (int k = 0; k < BSW; ++k) cg[k] = cgp[k];
+#pragma unroll
+                for (int k = 0; k < BSW; ++k) cs[k] = csp[k];
+                double d = s_sw[0];
+#pragma unroll 1
+                for (int pb2 = 0; pb2 < 8; pb2 += 2) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int pb = pb2 + h;
+                        const bool prow = (g == pb), pcol = (s == pb);
+#pragma unroll
+                        for (int q = 0; q < BSW; ++q) {
+                            const int pv = pb * BSW + q;
+                            const int nsl = (((h * BSW + q) & 1) ^ 1) * NN;   // the next pivot's slot (2 BSW pb2 is even)
+                            ok = ok && (d > 0.0);
+                            const double dinv = rcp_nr(d);
+                            // f = c_i dinv: the update's factor is -f (the fma's source modifier: fma3n), the new pivot
+                            // column is f itself
+                            double f[BSW];
+#pragma unroll
+                            for (int k = 0; k < BSW; ++k) f[k] = cg[k] * dinv;
+                            if (prow) {
+                                // the pivot row: K_pj <- dinv c_j + 0 (factor -(-dinv)), K_pp <- -dinv
+                                f[q] = -dinv;
+#pragma unroll
+                                for (int l = 0; l < BSW; ++l) Kb[q * BSW + l] = 0.0;
+                            }
+                            // the next pivot's column first, published at once
+                            const int q1 = (q + 1) % BSW;
+#pragma unroll
+                            for (int k = 0; k < BSW; ++k) Kb[k * BSW + q1] = fma3n(f[k], cs[q1], Kb[k * BSW + q1]);
+                            if (pv + 1 < NN && (q + 1 < BSW ? pcol : (s == pb + 1))) {
+                                double* const nb = s_sw + nsl + BSW * g;
+#pragma unroll
+                                for (int k = 0; k < BSW; ++k) nb[k] = Kb[k * BSW + q1];
+                            }
+                            __syncthreads();
+                            double ng[BSW], ns[BSW];
+#pragma unroll
+                            for (int k = 0; k < BSW; ++k) ng[k] = cgp[nsl + k];
+#pragma unroll
+                            for (int k = 0; k < BSW; ++k) ns[k] = csp[nsl + k];
+                            const double nd = s_sw[nsl + pv + 1];
+                            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                            for (int k = 0; k < BSW; ++k) {
+#pragma unroll
+                                for (int l = 0; l < BSW; ++l)
+                                    if (l != q1) Kb[k * BSW + l] = fma3n(f[k], cs[l], Kb[k * BSW + l]);
+                            }
+                            if (pcol) {
+#pragma unroll
+                                for (int k = 0; k < BSW; ++k) Kb[k * BSW + q] = f[k];
+                            }
+#pragma unroll
+                            for (int k = 0; k < BSW; ++k) {
+                                cg[k] = ng[k];
+                                cs[k] = ns[k];
+                            }
+                            d = nd;
+                        }
+                    }
+                }
+                // K^-1 = -(swept K); then back to rows for the ADMM (Kmul and the rest keep the row-per-lane form):
+                // in round k every lane writes local row k of its block to a row-major staging area (8 rows, stride
+                // ST2) in the scratch region -- the pivot columns are dead after the last pivot, the F slots and the
+                // window since the condensing -- and the lanes r with r % BSW == k read row r whole, under an exec
+                // mask (lds_load10_masked; lanes >= NN read row 0's slot: defined values they never use).
+#pragma unroll
+                for (int i = 0; i < BSW * BSW; ++i) Kb[i] = -Kb[i];
+                static_assert(NN == 40, "the masked row read is written for 2 x 10 ds_read_b128");
+                const int rk = tq % BSW, rg = (tq < NN) ? tq / BSW : 0;
+                typedef __attribute__((address_space(3))) double* LdsD;
+                const unsigned ra = (unsigned)(__UINTPTR_TYPE__)(LdsD)(s_u + rg * ST2);
+                v2d_t kr[NN / 2];
+#pragma unroll
+                for (int i = 0; i < NN / 2; ++i) kr[i] = v2d_t{0.0, 0.0};
+#pragma unroll
+                for (int k = 0; k < BSW; ++k) {
+                    __syncthreads();
+                    double* const wr = s_u + g * ST2 + BSW * s;
+#pragma unroll
+                    for (int l = 0; l < BSW; ++l) wr[l] = Kb[k * BSW + l];
+                    __syncthreads();
+                    const unsigned long long rm = __ballot(rk == k);
+                    lds_load10_masked<0>(ra, rm, kr);
+                    lds_load10_masked<160>(ra, rm, kr + 10);
+                }
+#pragma unroll
+                for (int i = 0; i < NN / 2; ++i) {
+                    Krow[2 * i] = kr[i].x;
+                    Krow[2 * i + 1] = kr[i].y;
+                }
+            } else if constexpr (WAVES == 1 && NN <= 42 && TGMPC_SWEEP_PAIR) {
                 // One-wave sweep in 2 x 2 pivot blocks (the row-split kernel's block, mpc_split.h): pivots p, p + 1
                 // (p even; n = 2N is even, so no block straddles a padding pivot) are eliminated together,
                 //   a = K_pp, b = K_p+1,p, c = K_p+1,p+1; 1/a; d2 = c - (b/a) b; 1/d2;
@@ -1801,8 +1942,10 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             // (L2W: the pivot columns share the exchange region -- no wave writes an exchange slot before the
             // other has read the last pivot row)
             if constexpr (L2W) __syncthreads();
+            if constexpr (!SW2D) {
 #pragma unroll
-            for (int j = 0; j < NN; ++j) Krow[j] = -Krow[j];
+                for (int j = 0; j < NN; ++j) Krow[j] = -Krow[j];
+            }
             toc(cyc_sweep);
 #if TGMPC_PRIO_SWEEP
             if (FUSED) __builtin_amdgcn_s_setprio(0);
