@@ -1,4 +1,4 @@
-"""The row-split kernel's block sweep (csrc/mpc_split.h, TGMPC_SPLIT_BLOCK), restated per row in numpy: for a block P of
+"""The row-split kernel's block sweep (csrc/mpc_split.h, pivots in pairs), restated per row in numpy: for a block P of
 m pivots every row forms the block's LDL' in the sequential sweep's elimination order and its coefficient vector
 w = D^-1 z (z = -K[r][P] outside the block, e_k on the block's k-th pivot row), then row r <- base + sum_k w_k K[.][p+k]
 (base = row r, or an exact zero row on the pivot rows; the pivot rows' entries are the published column values) and

@@ -22,18 +22,6 @@
 #ifndef TGMPC_PRIO_ITERS
 #define TGMPC_PRIO_ITERS 100   // fused run: ADMM iterations after which a solve's wave takes issue priority
 #endif
-#ifndef TGMPC_PRIO_SWEEP
-#define TGMPC_PRIO_SWEEP 0     // fused run: factorization sweeps at priority 2
-#endif
-#ifndef TGMPC_PRIO_LAG
-#define TGMPC_PRIO_LAG 0       // fused run: items of instances >= this many steps behind the draw front run at priority 3
-#endif
-#ifndef TGMPC_PRIO_HEAVY
-#define TGMPC_PRIO_HEAVY 0     // fused run: items of the heavy (lead) ranks run at priority 3 from their start
-#endif
-#ifndef TGMPC_PRIO_RANK
-#define TGMPC_PRIO_RANK 0      // fused run: heaviest ranks (per mille of B) whose items run at priority 2
-#endif
 
 #ifndef TGMPC_KCH
 #define TGMPC_KCH 8            // CMP: broadcast values per chunk of the ADMM mat-vec
@@ -48,16 +36,10 @@
 #define TGMPC_L2W_WPE 2        // waves per SIMD the lean two-wave instance is built for
 #endif
 #ifndef TGMPC_KCH_W2
-#define TGMPC_KCH_W2 8         // fused one-wave instance at 2 waves per SIMD: broadcast values per mat-vec chunk (0: all)
+#define TGMPC_KCH_W2 8         // fused one-wave instance at 2 waves per SIMD: broadcast values per mat-vec chunk
 #endif
 #ifndef TGMPC_PCH_W2
-#define TGMPC_PCH_W2 4         // fused one-wave instance at 2 waves per SIMD: pivot-row double2 per chunk (0: all)
-#endif
-#ifndef TGMPC_RCH80
-#define TGMPC_RCH80 1          // capacity 80, one wave per SIMD: Ruiz reads the broadcast D in chunks of 8
-#endif
-#ifndef TGMPC_PMUL80
-#define TGMPC_PMUL80 1         // capacity 80, one wave per SIMD: the rolled P v of the 3-wave instance
+#define TGMPC_PCH_W2 4         // fused one-wave instance at 2 waves per SIMD: pivot-row double2 per chunk
 #endif
 #ifndef TGMPC_SWEEP_UNROLL
 #define TGMPC_SWEEP_UNROLL 8   // one-wave sweep, fused instances: pivots per unrolled loop body (1: rolled, NN register
@@ -69,65 +51,21 @@
 #ifndef TGMPC_SWEEP_UNROLL2
 #define TGMPC_SWEEP_UNROLL2 4  // two-wave sweep (capacity 80): the same
 #endif
-#ifndef TGMPC_SWEEP_PAIR
-#define TGMPC_SWEEP_PAIR 0     // one-wave sweep: pivots in 2 x 2 blocks (one barrier and one LDS round per pair; 0: single).
-                               // Round 6: all 133 GPU tests green with it, but 200 steps 16.0 M against 16.1 M single
-                               // (20 steps within noise, +20 B/lane scratch): off -- same instructions per pivot
-#endif
 #ifndef TGMPC_SWEEP_2D
 #define TGMPC_SWEEP_2D 1       // fused capacity-40 instance at 2 waves per SIMD: K^-1 swept as 8 x 8 blocks of (NN/8)^2 entries, one
 #endif                         // block per lane, all 64 lanes busy (0: the row-per-lane receiver sweep); same values bit for bit
-#ifndef TGMPC_PAIR_CH
-#define TGMPC_PAIR_CH 4        // one-wave pair sweep: pivot-row entries (double2 of the two rows) per chunk
-#endif
 #define TGMPC_PRAGMA_(x) _Pragma(#x)
 #define TGMPC_PRAGMA(x) TGMPC_PRAGMA_(x)
-#ifndef TGMPC_RECV2
-#define TGMPC_RECV2 1          // capacity 80, one wave per SIMD: the receiver-lane sweep (one fma per entry and pivot)
-#endif
-#ifndef TGMPC_COND80
-#define TGMPC_COND80 1         // capacity 80, one wave per SIMD: the condensing reads the F rows in chunks of 8 (round 5,
-                               // under the max-ILP scheduler: config 3 0.967 -> 0.993 M, profiles/r05_cap80_knobs_ab.txt)
-#endif
-#ifndef TGMPC_PMUL_W2
-#define TGMPC_PMUL_W2 0        // one-wave fused instances at 2 waves per SIMD: the rolled P v as well
-#endif
-#ifndef TGMPC_RESMAX2
-#define TGMPC_RESMAX2 1        // two-wave residual checks: the maxima by an LDS-transposed reduction (0: block_max)
-#endif
-#ifndef TGMPC_KMC80
-#define TGMPC_KMC80 4          // independent FMA chains of the capacity-80 ADMM mat-vec (every capacity-80 instance,
-                               // fused and per-step alike, so they stay bit-identical): 8 measured 0.87 M vs 0.93 M
-                               // at config 3 (and with 40-value chunks 0.85 M; round 5, profiles/r05_kmc80_ab_n40.txt)
-#endif
-// (capacity <= 64 uses 4 chains, fixed: the round-5 build knob for 8 changed only some instances' summation order and
-// so broke the fused / per-step bit-identity; 8 chains had measured 9.2-9.5 M vs 13.0-13.5 M steps/s there anyway)
 #ifndef TGMPC_KCH80
 #define TGMPC_KCH80 40         // capacity 80, one wave per SIMD: broadcast values per chunk of the ADMM mat-vec (round 5,
                                // under the max-ILP scheduler: 40 0.965-0.969 M at config 3, 16 0.952, 80 0.946, 20 0.935,
                                // 8 0.933; profiles/r05_cap80_knobs_ab.txt)
 #endif
 #ifndef TGMPC_PCH80
-#define TGMPC_PCH80 4          // capacity 80, one wave per SIMD: pivot-row double2 per chunk of the sweep (0: whole row)
+#define TGMPC_PCH80 4          // capacity 80, one wave per SIMD: pivot-row double2 per chunk of the sweep
 #endif
 #ifndef TGMPC_PCH2
 #define TGMPC_PCH2 4           // L2W: pivot-row double2 per chunk of the two-wave sweep
-#endif
-#ifndef TGMPC_RECV2_L2W
-#define TGMPC_RECV2_L2W 1      // L2W: the receiver sweep as well (scratch 1,864 -> 396 B/lane; still opt-in)
-#endif
-#ifndef TGMPC_RUIZ_CUM
-#define TGMPC_RUIZ_CUM 0       // capacity <= 40: Ruiz norms from the cumulative scaling, the row scaled once (measured
-                               // neutral at 20 steps, r04: off, keeping OSQP's in-place order)
-#endif
-#ifndef TGMPC_PSPAD
-#define TGMPC_PSPAD 2          // FULLP: row stride NN + TGMPC_PSPAD doubles (0: NN, the bank-conflicted stride)
-#endif
-#ifndef TGMPC_FULLP
-#define TGMPC_FULLP 1          // one-wave, non-lean instances: the scaled P in LDS as the full symmetric matrix (row-major)
-#endif
-#ifndef TGMPC_COND_SPARSE
-#define TGMPC_COND_SPARSE 1    // closed loop: the condensing skips A_k's structural zeros and P's all-zero MFMA tiles
 #endif
 
 namespace tgmpc {
@@ -152,11 +90,12 @@ namespace tgmpc {
 // and the step entry point (traj_mpc_step_batch: one launch per call instead of rollout + Jacobian + solve; the
 // records are copied to the workspace's A/B/g for X_opt).  Same values as rollout_kernel + jac_kernel.
 template <int NN, bool CLOSED, bool FUSED = false, bool DIAG = true, int WPS = 2, bool INLIN = FUSED>
-// (capacity 64: the row of K^-1 and its broadcast vector alone are 256 VGPRs -- one wave per SIMD; capacity 80,
-// two waves per instance: one wave per SIMD, or, fused with WPS = 2, two -- the lean two-wave instance below)
+// (one wave per instance: WPS waves per SIMD; capacity 80, two waves per instance: one wave per SIMD, or, fused
+// with WPS = 2, two -- the lean two-wave instance below)
 __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_per_eu(
-    NN <= 40 ? WPS : ((FUSED && NN > 64 && WPS >= 2) ? TGMPC_L2W_WPE : 1)))) void solve_kernel(const KArgs a0) {
+    NN <= 64 ? WPS : ((FUSED && WPS >= 2) ? TGMPC_L2W_WPE : 1)))) void solve_kernel(const KArgs a0) {
     constexpr int WAVES = (NN + 63) / 64;
+    static_assert(WAVES <= 2, "one or two waves per instance");
     constexpr int NT = WAVES * 64;
     constexpr int NM = NN / 2;          // max horizon
     constexpr int NP0 = NN * (NN + 1) / 2;
@@ -180,23 +119,21 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // arithmetic (each lane reads exactly the entries it read from the packed triangle, which every writer keeps
     // symmetric bit for bit), so the results do not change.  Costs (NN - 1) NN / 2 doubles more LDS: 6.2 KB at
     // capacity 40 -- the fused 2-wave instance's image grows to 19.0 KB, still 8 workgroups per CU; the 3-wave
-    // instance's 12.8 KB budget, the per-step kernels' staging tail and capacity 64 keep the packed form.
+    // instance's 12.8 KB budget and the per-step kernels' staging tail keep the packed form.
     // (and the fused capacity-80 instance at one wave per SIMD: 73 KB per workgroup, 2 per CU as before)
-    constexpr bool FULLP = TGMPC_FULLP && !LEAN && ((CMP && NN <= 40) || (FUSED && WAVES == 2 && !L2W));
+    constexpr bool FULLP = FUSED && !LEAN;
     // FULLP row stride PS = NN + 2 doubles (2 PS = 4 mod 8 dwords): a row-per-lane 16-byte read puts 16 consecutive
     // lanes on 16 distinct 4-bank groups (stride NN = 40 maps every 4th lane to the same banks: 16-way conflicts)
-    constexpr int PS = FULLP ? NN + TGMPC_PSPAD : NN;
+    constexpr int PSPAD = 2;
+    constexpr int PS = FULLP ? NN + PSPAD : NN;
     // SW2D: the factorization sweep over an 8 x 8 grid of lanes, each holding a BSW x BSW block of K (see the sweep).
-    // The fused capacity-40 instance at two waves per SIMD; the 3-wave, lean, pair-sweep, per-step and other
+    // The fused capacity-40 instance at two waves per SIMD; the 3-wave, lean, per-step and other
     // capacities' instances keep the row-per-lane sweep (identical arithmetic: they cross-check this one).
-    constexpr bool SW2D = TGMPC_SWEEP_2D && !TGMPC_SWEEP_PAIR && CMP && !LEAN && FULLP && NN == 40;
+    constexpr bool SW2D = TGMPC_SWEEP_2D && CMP && !LEAN && FULLP && NN == 40;
     constexpr int BSW = NN / 8;
     constexpr int ST2 = NN + 2;   // SW2D: row stride of the staging area that turns blocks back into rows
-    static_assert(!FULLP || TGMPC_PSPAD != 2 || (2 * PS) % 8 == 4, "conflict-free row stride");
+    static_assert(!FULLP || (2 * PS) % 8 == 4, "conflict-free row stride");
     constexpr int NP = FULLP ? NN * PS : NP0;
-    // cumulative Ruiz scaling (the scaling pass) up to capacity 40; the N = 40 problems (condition ~1e9) keep OSQP's
-    // in-place order -- their exact-mode parity bar for unpolished points (0.1) did not hold with it
-    constexpr bool RUIZ_CUM = TGMPC_RUIZ_CUM && NN <= 40;
     __shared__ double s_pref0[(CMP || L2W) ? 2 : 3 * (NM + 1)];
     __shared__ double s_vref0[(CMP || L2W) ? 2 : NM + 1];
     __shared__ double s_x0[6], s_up[2];
@@ -207,7 +144,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // NN wide: the spare lanes read the next row's values, or lane CS-1's pair, and never use them)
     constexpr int CS = (WAVES == 1 || L2W) ? NN : NT;
     // the two-wave receiver sweep (capacity 80; the lean two-wave instance too): rows start shifted by SP2 lanes
-    constexpr bool RECV2 = WAVES == 2 && (!L2W || TGMPC_RECV2_L2W) && TGMPC_RECV2;
+    constexpr bool RECV2 = WAVES == 2;
     constexpr int SP2 = 64 * WAVES - NN;
     constexpr int NCOLD = 11 * CS;   // 5 single rows + 3 pair rows (see the cold values below)
     constexpr int NLIN = 54 * NM;
@@ -225,8 +162,8 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // two waves 3 fixed slots (4, 5, 6) for the ADMM loop's three exchanges, so no rotating index lives
     // across that loop (at NN = 80 it was spilled and reloaded from scratch in every exchange)
     constexpr int NEX = (WAVES > 1) ? (4 * NN + 3 * NT > 6 * NN ? 4 * NN + 3 * NT : 6 * NN) : (CMP ? 4 * NN : 6 * NN);
-    // sweep pivot columns: 2 slots of 2 NN + 2 doubles (single pivots), or of 2 NN double2 (one-wave pair sweep)
-    constexpr int NSW = (WAVES == 1 && TGMPC_SWEEP_PAIR) ? 8 * NN : 2 * (2 * NN + 2);
+    // sweep pivot columns: 2 slots of 2 NN + 2 doubles
+    constexpr int NSW = 2 * (2 * NN + 2);
     constexpr int FS = 16 * ((NN + 15) / 16);
     constexpr int NFS = (WAVES > 1) ? 0 : (CMP ? 1 : 2) * 4 * FS;   // condensing F_k rows: slots of 4 x FS (one wave)
     // CMP: one scratch region for the exchange / broadcast slots (ADMM, Ruiz, polish), the sweep's pivot
@@ -256,6 +193,14 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     double* const s_sc = CMP ? s_u + NFS + 4 * (NM + 1) : (L2W ? s_big + NLIN + 4 * (NM + 1) : s_sc0);
     __shared__ double s_red[WAVES > 1 ? 16 * WAVES : 2];
     __shared__ int s_flag[4];
+    // The static LDS image of a fused one-wave instance (CMP): s_big, s_u, s_x0, s_up, s_xh, s_item (padded to 8 bytes)
+    // and s_flag -- the 2-double placeholders above and s_red have no reader there and take no space.  It decides the
+    // occupancy the kernel is tuned for, of a CU's 160 KB: at capacity 40, 8 workgroups (2 waves per SIMD) need
+    // <= 20,480 B and 12 (the 3-wave instance) <= 12,800 B; the images are 19,784 B and 12,776 B, the compiler's
+    // group_segment_fixed_size.
+    constexpr int LDS_CMP = sizeof(s_big) + sizeof(s_u) + sizeof(s_x0) + sizeof(s_up) + sizeof(s_xh) + 8 + sizeof(s_flag);
+    static_assert(!(CMP && NN == 40 && WPS == 2) || LDS_CMP <= 20480, "LDS image: 8 workgroups per CU");
+    static_assert(!(CMP && NN == 40 && WPS >= 3) || LDS_CMP <= 12800, "LDS image: 12 workgroups per CU");
 
     // Fused closed loop (traj_closed_loop_run): nsteps steps of this instance in one launch -- the
     // state, u_prev and the warm-start rho stay on chip and the linearization runs in the
@@ -381,14 +326,6 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         // issue priority (s_setprio): the wave that works on a long chain gets the SIMD first -- see the
         // ADMM loop; every item starts at the default priority
         __builtin_amdgcn_s_setprio(0);
-#if TGMPC_PRIO_RANK > 0
-        if (a.perm && rank * 1000 < a.B * TGMPC_PRIO_RANK) __builtin_amdgcn_s_setprio(2);
-#endif
-#if TGMPC_PRIO_HEAVY
-        // the heavy instances (the queue's lead set: the most ADMM iterations in the previous launch) are the
-        // launch's critical chains -- their items issue first for the whole item
-        if (a.perm && rank < a.lead_h) __builtin_amdgcn_s_setprio(3);
-#endif
         if (threadIdx.x == 0 && step > 0) {
             int spins = 0;
             while (__hip_atomic_load(&a.queue[2 + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < step) {
@@ -400,13 +337,6 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 }
             }
         }
-#if TGMPC_PRIO_LAG > 0
-        // the queue's draw front when this item can start: an instance that lags the front by whole
-        // steps is the launch's critical chain (the run ends with it) -- its wave issues first
-        if (threadIdx.x == 0) s_item = __hip_atomic_load(&a.queue[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (s_item / a.B - step >= TGMPC_PRIO_LAG) __builtin_amdgcn_s_setprio(3);
-#endif
         __syncthreads();
         if (dbg_items && threadIdx.x == 0) {   // diagnostics: item timeline (traj_debug_set_item_stamps)
             dbg_items[4 * (size_t)q + 1] = __builtin_amdgcn_s_memrealtime();
@@ -630,7 +560,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // lane t carries column t of the input sensitivity G_k (6-vector); the free response xh_k and
     // its tracking errors e_k are uniform and computed by every lane.  With the weights split as
     // sqrt(2W), F_k = sqrt(2W) C_k G_k (3 x n per stage) and P = sum_k F_k' F_k.
-    //   one wave (NN <= 64): P accumulates on the matrix cores -- per stage one k=4 step of
+    //   one wave: P accumulates on the matrix cores -- per stage one k=4 step of
     //     v_mfma_f64_16x16x4 per upper-triangle 16x16 tile (rows 0..2 of the step = F_k, row 3 = 0);
     //     each lane reads just the 1-3 F values of its operand slots;
     //   two waves (NN = 80): each lane accumulates its row, F_t F_j (3 FMAs per entry).
@@ -687,7 +617,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         // and adds the unit ones (fma(1, x, v) = v + x, fma(0, x, v) = v for finite x): the same values (up to
         // the sign of a zero) with 16 fmas and 3 adds instead of 36 fmas.  The QP entry point (caller's A_k) and
         // the step keep the full chain.
-        constexpr bool SPARSE_A = CLOSED && TGMPC_COND_SPARSE;
+        constexpr bool SPARSE_A = CLOSED;
         auto arow = [&](const double* Ak, int r, const double* x, double v) -> double {
             if constexpr (SPARSE_A) {
                 if (r <= 1) {
@@ -749,17 +679,11 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             qi += sw0 * F0 * e0 + sw1 * F1 * e1 + sw2 * F2 * e2;
             if constexpr (WAVES == 1) {
                 double* fb = s_F + (CMP ? 0 : (k & 1) * 4 * FS);   // 2 rotating slots (CMP: 1); row 3 and columns >= n stay 0
-#ifdef TGMPC_EXP_NO_FSYNC
-                double opv[NB];
-#pragma unroll
-                for (int ib = 0; ib < NB; ++ib) opv[ib] = F0 + ib * F1 + F2;
-#else
                 if (own) { fb[t] = F0; fb[FS + t] = F1; fb[2 * FS + t] = F2; }
                 __syncthreads();
                 double opv[NB];
 #pragma unroll
                 for (int ib = 0; ib < NB; ++ib) opv[ib] = fb[mr * FS + 16 * ib + mc];
-#endif
                 // F_k's columns >= 2 (k + 1) are exact zeros (the inputs of later stages): a tile whose column block
                 // starts there adds +-0 to its accumulator and is skipped (bit-identical; stages 0..7 touch one
                 // tile of 6 at capacity 40, 56 MFMAs per instance instead of 120 at N = 20)
@@ -768,50 +692,36 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 for (int ib = 0; ib < NB; ++ib)
 #pragma unroll
                     for (int jb = ib; jb < NB; ++jb, ++ti)
-#ifdef TGMPC_EXP_NO_MFMA
-                        acc[ti][0] += opv[ib] * opv[jb];
-#else
-                        if (!TGMPC_COND_SPARSE || 16 * jb < 2 * k + 2)
+                        if (16 * jb < 2 * k + 2)
                             acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(opv[ib], opv[jb], acc[ti], 0, 0, 0);
-#endif
             } else {
                 double* buf = s_ex + (xb & 1) * 3 * NN;   // 2 rotating slots of 3*NN
                 xb++;
                 if (own) { buf[t] = F0; buf[NN + t] = F1; buf[2 * NN + t] = F2; }
                 __syncthreads();
-                if constexpr (L2W || TGMPC_COND80) {
-                    // the three F rows in chunks of 8 entries, each chunk's reads then its FMAs (the scheduler would
-                    // otherwise issue all 240 reads beside the 160 registers of Prow); same FMAs, same order
-                    const double2* b2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(buf, 16));
+                // the three F rows in chunks of 8 entries, each chunk's reads then its FMAs (the scheduler would
+                // otherwise issue all 240 reads beside the 160 registers of Prow); same FMAs, same order.
+                // F_k's columns >= 2 (k + 1) are exact zeros (the inputs of later stages do not move x_{k+1}):
+                // their three fmas add exact zeros to the row and are skipped, 8 columns at a time (a uniform
+                // branch; bit-identical -- about half of the stage loop's fmas at N = 40)
+                const double2* b2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(buf, 16));
 #pragma unroll
-                    for (int c0 = 0; c0 < NN; c0 += 8) {
-                        if (TGMPC_COND_SPARSE && c0 >= 2 * k + 2) continue;   // F_k's zero columns (see below)
-                        double2 f0[4], f1[4], f2[4];
+                for (int c0 = 0; c0 < NN; c0 += 8) {
+                    if (c0 >= 2 * k + 2) continue;
+                    double2 f0[4], f1[4], f2[4];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            f0[i] = b2[c0 / 2 + i];
-                            f1[i] = b2[(NN + c0) / 2 + i];
-                            f2[i] = b2[(2 * NN + c0) / 2 + i];
-                        }
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            Prow[c0 + 2 * i] = fma(F0, f0[i].x, fma(F1, f1[i].x, fma(F2, f2[i].x, Prow[c0 + 2 * i])));
-                            Prow[c0 + 2 * i + 1] = fma(F0, f0[i].y, fma(F1, f1[i].y, fma(F2, f2[i].y, Prow[c0 + 2 * i + 1])));
-                        }
-                        __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
+                    for (int i = 0; i < 4; ++i) {
+                        f0[i] = b2[c0 / 2 + i];
+                        f1[i] = b2[(NN + c0) / 2 + i];
+                        f2[i] = b2[(2 * NN + c0) / 2 + i];
                     }
-                } else {
-                    // F_k's columns >= 2 (k + 1) are exact zeros (the inputs of later stages do not move x_{k+1}):
-                    // their three fmas add exact zeros to the row and are skipped, 8 columns at a time (a uniform
-                    // branch; bit-identical -- about half of the stage loop's fmas at N = 40)
 #pragma unroll
-                    for (int c0 = 0; c0 < NN; c0 += 8) {
-                        if (TGMPC_COND_SPARSE && c0 >= 2 * k + 2) continue;
-#pragma unroll
-                        for (int j = c0; j < c0 + 8; ++j)
-                            Prow[j] = fma(F0, buf[j], fma(F1, buf[NN + j], fma(F2, buf[2 * NN + j], Prow[j])));
+                    for (int i = 0; i < 4; ++i) {
+                        Prow[c0 + 2 * i] = fma(F0, f0[i].x, fma(F1, f1[i].x, fma(F2, f2[i].x, Prow[c0 + 2 * i])));
+                        Prow[c0 + 2 * i + 1] = fma(F0, f0[i].y, fma(F1, f1[i].y, fma(F2, f2[i].y, Prow[c0 + 2 * i + 1])));
                     }
+                    __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
                 }
             }
         }
@@ -947,7 +857,6 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             cn = vmax(vmax(c4[0], c4[1]), vmax(c4[2], c4[3]));
         }
         const double ninv = 1.0 / n;   // (the mean column norm: cdiv, mpc_common.h)
-        const double* dvb_last = nullptr;   // RUIZ_CUM: the last pass's broadcast of D
         for (int it = 0; it < c.scaling_iters; ++it) {
             double Er_up = exch(Er, +2);     // E of rate row t+2
             double D_dn = exch(D, -2);       // D of variable t-2
@@ -959,29 +868,11 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             double Etb = rcp_n(sqrt_n(limit_scaling(fabs(a_b))));
             double Etr = rcp_n(sqrt_n(limit_scaling(vmax_abs2(a_r, a_rm))));
             // the broadcast D read in chunks of RCH, each chunk's reads in flight at once (CMP: 8, so that the
-            // row of P and the chunk fit the 3-wave register budget; otherwise the whole vector)
+            // row of P and the chunk fit the 3-wave register budget; capacity 80: 8 as well; the per-step one-wave
+            // kernels: the whole vector)
             double c4[4] = {0.0, 0.0, 0.0, 0.0};
-            constexpr int RCH = (CMP || LEAN || (WAVES > 1 && TGMPC_RCH80)) ? 8 : NN;
+            constexpr int RCH = (CMP || WAVES > 1) ? 8 : NN;
             static_assert(NN % RCH == 0, "chunked broadcast");
-            if constexpr (RUIZ_CUM) {
-            // The row stays the unscaled P row; the pass's norms come from the CUMULATIVE scaling:
-            // max_j |P_tj D_j| D_t (one product and one max per entry instead of two products and a max); the row
-            // is scaled once after the last pass, P_tj (D_t D_j) cs -- symmetric bit for bit, as the full-P image
-            // and the packed triangle need.  (OSQP scales P in place every pass; the scaled P agrees to the last
-            // bits, the parity tests' bar.)
-            D *= Dt;
-            const double* dvb = bcast(D);
-            dvb_last = dvb;
-#pragma unroll
-            for (int c0 = 0; c0 < NN; c0 += RCH) {
-                double Dv[RCH];
-                lds_load_all<RCH>(dvb + c0, Dv);
-#pragma unroll
-                for (int j = 0; j < RCH; ++j) c4[(c0 + j) & 3] = vmax_abs(c4[(c0 + j) & 3], Prow[c0 + j] * Dv[j]);
-            }
-            cn = D * vmax(vmax(c4[0], c4[1]), vmax(c4[2], c4[3]));
-            qi *= Dt;
-            } else {
             const double* dvb = bcast(Dt);
 #pragma unroll
             for (int c0 = 0; c0 < NN; c0 += RCH) {
@@ -997,7 +888,6 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             cn = vmax(vmax(c4[0], c4[1]), vmax(c4[2], c4[3]));
             qi *= Dt;
             D *= Dt;
-            }
             Eb *= Etb;
             Er *= Etr;
             // cost scaling of the scaled data cs (P, q)
@@ -1008,24 +898,8 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             ct = rcp_n(limit_scaling(ct));
             cs *= ct;
         }
-        if constexpr (RUIZ_CUM) {
-            if (dvb_last) {   // the last pass's broadcast of the final D (no LDS write since)
-                constexpr int RCH = (CMP || LEAN) ? 8 : NN;
 #pragma unroll
-                for (int c0 = 0; c0 < NN; c0 += RCH) {
-                    double Dv[RCH];
-                    lds_load_all<RCH>(dvb_last + c0, Dv);
-#pragma unroll
-                    for (int j = 0; j < RCH; ++j) Prow[c0 + j] = (Prow[c0 + j] * (D * Dv[j])) * cs;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < NN; ++j) Prow[j] *= cs;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NN; ++j) Prow[j] *= cs;
-        }
+        for (int j = 0; j < NN; ++j) Prow[j] *= cs;
         qi *= cs;
         const double csinv = uniformize(1.0 / cs);   // uniform (held in SGPRs, not in VGPRs)
         const double D_dn = exch(D, -2);
@@ -1125,7 +999,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                         sa[2 * i + 1] = fma(pv[i].y, vv[i].y, sa[2 * i + 1]);
                     }
                 }
-            } else if constexpr (LEAN || (WAVES > 1 && TGMPC_PMUL80) || (CMP && TGMPC_PMUL_W2)) {
+            } else if constexpr (LEAN || WAVES > 1) {
                 // a ROLLED loop over blocks of 8 (the row of K^-1 stays live across this: fully unrolled, the
                 // scheduler issues all 80 reads at once and the ADMM loop around it spills); same sums, same order
                 static_assert(NN % 8 == 0, "Pmul blocks");
@@ -1160,15 +1034,15 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         double Krow[NN];
         double Kb[SW2D ? BSW * BSW : 1];   // SW2D: the lane's block of K during the factorization, row-major
         auto Kmul = [&](double v, int slot = -1) -> double {  // (K^{-1} v)_t, KC independent FMA chains
-            // (4 at capacity <= 64 -- round 2 chose 4: one wave issues an f64 op about every 8 cycles, 8 chains
-            // measured far slower in the fused instance; TGMPC_KMC80 at capacity 80, default 4)
-            constexpr int KC = NN <= 64 ? 4 : TGMPC_KMC80;
-            static_assert(KC == 4 || KC == 8, "TGMPC_KMC80: 4 or 8 chains");
+            // (round 2 chose 4: one wave issues an f64 op about every 8 cycles, 8 chains measured far slower in the
+            // fused instance, and at capacity 80 0.87 M vs 0.93 M at config 3, round 5; every instance of a capacity
+            // uses the same chains, so fused and per-step stay bit-identical)
+            constexpr int KC = 4;
             double sa[KC];
 #pragma unroll
             for (int i = 0; i < KC; ++i) sa[i] = 0.0;
             const double* vbuf = (slot >= 0) ? bcast_at(v, slot) : bcast(v);
-            if constexpr (NN <= 64 && !CMP) {
+            if constexpr (WAVES == 1 && !CMP) {
                 double vb[NN];
                 lds_load_all<NN>(vbuf, vb);
 #pragma unroll
@@ -1177,7 +1051,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 // NN = 80: the whole vector in flight (160 VGPRs beside the 160 of Krow) spills inside the
                 // ADMM loop; CMP: the 3-wave budget (168) holds the row and a chunk.  CH values at a time
                 // (the next chunk's reads issued before this chunk's FMAs), same FMA order
-                constexpr int CH = LEAN ? TGMPC_KCH : (CMP ? (TGMPC_KCH_W2 > 0 ? TGMPC_KCH_W2 : NN) : TGMPC_KCH80);
+                constexpr int CH = LEAN ? TGMPC_KCH : (CMP ? TGMPC_KCH_W2 : TGMPC_KCH80);
                 static_assert(NN % CH == 0 && CH % 2 == 0, "chunked broadcast");
                 const double2* v2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(vbuf, 16));
                 double2 vb[CH / 2];
@@ -1205,9 +1079,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                     __builtin_amdgcn_sched_group_barrier(0x002, CH, 0);
                 }
             }
-            double r;
-            if constexpr (KC == 8) r = ((sa[0] + sa[1]) + (sa[2] + sa[3])) + ((sa[4] + sa[5]) + (sa[6] + sa[7]));
-            else r = (sa[0] + sa[1]) + (sa[2] + sa[3]);
+            double r = (sa[0] + sa[1]) + (sa[2] + sa[3]);
             // (opaque: keeps the compiler from turning the select into a branch around the whole mat-vec)
             asm volatile("" : "+v"(r));
             return own ? r : 0.0;
@@ -1271,7 +1143,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = nan[i] ? __builtin_nan("") : mv[i];
                 __syncthreads();
-            } else if constexpr (TGMPC_RESMAX2 && WAVES == 2 && !LEAN) {
+            } else if constexpr (!LEAN) {
                 // two waves: the same transposed reduction over the exchange buffers (free here: every product of
                 // this check is in registers once the first barrier is passed) -- 8 values x NN rows, lane 8 i + p
                 // of wave 0 takes rows [p NN/8, (p+1) NN/8) of value i, three DPP steps, 8 maxima back; block_max's
@@ -1450,9 +1322,9 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
 #pragma unroll
                         for (int j = 0; j < NN; ++j) Krow[j] = 0.0;
                     }
-                } else if (WAVES > 1 || t < NN) {
+                } else if (t < NN) {
 #pragma unroll
-                    for (int j = 0; j < NN; ++j) Krow[j] = (WAVES == 1 || t < NN) ? s_P[paddr(j, tt)] : 0.0;
+                    for (int j = 0; j < NN; ++j) Krow[j] = s_P[paddr(j, tt)];
                 } else {
 #pragma unroll
                     for (int j = 0; j < NN; ++j) Krow[j] = 0.0;
@@ -1474,9 +1346,6 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             // (K symmetric: K[pv][c] = K[c][pv]).  Padding pivots (>= n) are identity and exact.
             bool ok = true;
             tic();
-#if TGMPC_PRIO_SWEEP
-            if (FUSED) __builtin_amdgcn_s_setprio(2);   // the sweep's pivot chain is LDS-latency bound
-#endif
             if constexpr (SW2D) {
                 // One-wave sweep with K held as 8 x 8 blocks: lane 8 g + s holds the BSW x BSW block of rows
                 // BSW g .. and columns BSW s .., so all 64 lanes carry data (the row form below: NN of 64) and a
@@ -1598,105 +1467,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                     Krow[2 * i] = kr[i].x;
                     Krow[2 * i + 1] = kr[i].y;
                 }
-            } else if constexpr (WAVES == 1 && NN <= 42 && TGMPC_SWEEP_PAIR) {
-                // One-wave sweep in 2 x 2 pivot blocks (the row-split kernel's block, mpc_split.h): pivots p, p + 1
-                // (p even; n = 2N is even, so no block straddles a padding pivot) are eliminated together,
-                //   a = K_pp, b = K_p+1,p, c = K_p+1,p+1; 1/a; d2 = c - (b/a) b; 1/d2;
-                //   row lanes (u = K_tp, v = K_t,p+1): beta = (v - (u/a) b)/d2, alpha = (u - beta b)/a,
-                //     K_tj <- K_tj - alpha K_pj - beta K_p+1,j, and the block's columns <- (alpha, beta);
-                //   the two RECEIVER lanes (exact zero rows, as in the single form below) take the rows of the block
-                //     inverse G (g00 = 1/a + (b/a)^2/d2, g01 = -(b/a)/d2, g11 = 1/d2) times the pivot rows, and -G.
-                // Both pivot columns are published in one slot as double2 (K_rp, K_r,p+1) under the row r a lane
-                // holds, twice (rotation: the pivot rows in rotated order are the contiguous slice [p, p + NN));
-                // the registers rotate by two per block; receivers are lanes rl(p), rl(p) + 1 with the single form's
-                // rl (NN + p while p < 64 - NN, then the dropped lanes p - (64 - NN), re-zeroed once), so row r
-                // ends in lane (r + NN) mod 64 as there.  The same algebra as two single pivots with one barrier
-                // and one LDS round instead of two; the composed coefficients round differently in the last bits.
-                static_assert(NN % 2 == 0, "pairs of pivots");
-                constexpr int SB2 = 2 * NN;        // double2 per slot (indices rho, rho + NN)
-                static_assert(2 * 2 * SB2 <= NSW, "two slots of double2 columns");
-                constexpr int SPARE = 64 - NN;
-                constexpr int CH = LEAN ? TGMPC_PCH : TGMPC_PAIR_CH;
-                double2* const sw2 = reinterpret_cast<double2*>(__builtin_assume_aligned(s_sw, 16));
-                int rho = t < NN ? t : -1;    // row held by this lane (-1: zero or dropped)
-                if (t < NN) {
-                    const double2 c01 = make_double2(Krow[0], Krow[1]);
-                    sw2[t] = c01;
-                    sw2[t + NN] = c01;
-                }
-                constexpr int SWU = FUSED ? TGMPC_SWEEP_UNROLL : TGMPC_SWEEP_UNROLL_STEP;
-                constexpr int SWU2 = SWU >= 2 ? SWU / 2 : 1;
-#pragma unroll SWU2
-                for (int pv = 0; pv < NN; pv += 2) {
-                    if (NN > SPARE && pv == SPARE) {
-                        // lanes 0..SPARE-1 all pivoted (dropped rows): zero them, they receive next
-                        if (t < SPARE) {
-#pragma unroll
-                            for (int j = 0; j < NN; ++j) Krow[j] = 0.0;
-                        }
-                    }
-                    __syncthreads();
-                    const int o = (pv >> 1) & 1;
-                    // prow[j] = (K_p,p+j, K_p+1,p+j) (rotated; K_r,p = K_p,r)
-                    const double2* prow = sw2 + o * SB2 + pv;
-                    const double2 q0 = prow[0], q1 = prow[1];
-                    double2 cur[CH];
-#pragma unroll
-                    for (int i = 0; i < CH; ++i) if (2 + i < NN) cur[i] = prow[2 + i];
-                    const double a = q0.x, bb = q1.x, cc = q1.y;
-                    const double u = Krow[0], v = Krow[1];
-                    const double ainv = rcp_nr(a);
-                    const double tq = bb * ainv;
-                    const double d2 = fma(-tq, bb, cc);
-                    ok = ok && (a > 0.0) && (d2 > 0.0);
-                    const double d2inv = rcp_nr(d2);
-                    const int rl0 = pv < SPARE ? NN + pv : pv - SPARE;   // receiver lanes rl0, rl0 + 1 (uniform)
-                    const bool r0 = (t == rl0), r1 = (t == rl0 + 1);
-                    const double td = tq * d2inv;
-                    const double beta = fma(-(u * ainv), bb, v) * d2inv;
-                    const double alpha = fma(-beta, bb, u) * ainv;
-                    const double cA = r0 ? fma(td, tq, ainv) : (r1 ? -td : -alpha);
-                    const double cB = r0 ? -td : (r1 ? d2inv : -beta);
-                    rho = r0 ? pv : (r1 ? pv + 1 : ((t == pv || t == pv + 1) ? -1 : rho));
-                    // the next block's columns (registers 2, 3) first, published at once
-                    const double n2 = fma3(cA, cur[0].x, fma(cB, cur[0].y, Krow[2]));
-                    const double n3 = fma3(cA, cur[1].x, fma(cB, cur[1].y, Krow[3]));
-                    if (rho >= 0) {
-                        double2* const nb = sw2 + (o ^ 1) * SB2;
-                        const double2 nn = make_double2(n2, n3);
-                        nb[rho] = nn;
-                        nb[rho + NN] = nn;
-                    }
-                    // Krow[j - 2] <- cA (row p)[j] + cB (row p + 1)[j] + Krow[j], j = 4 .. NN-1, in chunks of CH
-                    // entries, the next chunk's reads issued before this chunk's FMAs
-#pragma unroll
-                    for (int c0 = 2; c0 < NN; c0 += CH) {
-                        double2 nx[CH];
-#pragma unroll
-                        for (int i = 0; i < CH; ++i) if (c0 + CH + i < NN) nx[i] = prow[c0 + CH + i];
-#pragma unroll
-                        for (int i = 0; i < CH; ++i) {
-                            const int j = c0 + i;
-                            if (j >= 4 && j < NN) Krow[j - 2] = fma3(cA, cur[i].x, fma(cB, cur[i].y, Krow[j]));
-                        }
-#pragma unroll
-                        for (int i = 0; i < CH; ++i) cur[i] = nx[i];
-                    }
-                    Krow[0] = n2;
-                    Krow[1] = n3;
-                    Krow[NN - 2] = -cA;
-                    Krow[NN - 1] = -cB;
-                }
-                // row r sits in lane (r + NN) mod 64: rotate it back to lane r
-                const int src = ((t + NN) & 63) << 2;
-#pragma unroll
-                for (int j = 0; j < NN; ++j) {
-                    const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(Krow[j]));
-                    const int hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(Krow[j]));
-                    Krow[j] = __hiloint2double(hi, lo);
-                    __builtin_amdgcn_sched_barrier(0);   // one register at a time (no batch of 80 temporaries)
-                }
-            } else if constexpr (WAVES == 1 && NN <= 42) {
+            } else if constexpr (WAVES == 1) {
                 // One-wave sweep, ONE fma per entry and pivot.  The new pivot row (K_pj / d) is not
                 // formed in place (that needs a second operation on the pivot lane only) but in a
                 // RECEIVER lane holding an exact zero row: every lane computes
@@ -1704,13 +1475,14 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 // be = -K_tp / d on row lanes, 1 / d on the receiver (0 + pr/d, exact), and the old
                 // pivot lane's row is dropped.  Receivers are the spare lanes NN..63 (pivots < 64-NN),
                 // then the former pivot lanes 0.. (re-zeroed once), so row r ends in lane (r + NN) mod
-                // 64 and one ds_bpermute rotation puts it back in lane r.  The values are those of the
-                // two-operation form bit for bit (fma(be, pr, 1 * K) and fma(1/d, pr, 0 * K)).
-                // Rotated registers as below (pivot column in register 0); the update is written as
+                // 64 and one ds_bpermute rotation puts it back in lane r.  The values are those of forming
+                // the pivot row in place, bit for bit (fma(be, pr, 1 * K) and fma(1/d, pr, 0 * K)).
+                // Rotated registers as above (pivot column in register 0); the update is written as
                 // three-address v_fma_f64 (fma3), so the rotation costs no register copies.
                 // Row lanes publish their column entry under the ROW they hold (rho), twice.
                 constexpr int SB = 2 * NN + 2;
                 constexpr int SPARE = 64 - NN;
+                static_assert(NN <= 2 * SPARE, "receivers: the spare lanes, then the first dropped rows' lanes");
                 int rho = t < NN ? t : -1;    // row held by this lane (-1: zero or dropped)
                 if (t < NN) {
                     s_sw[t] = Krow[0];
@@ -1734,7 +1506,8 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                     const double2* prow2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(prow, 16));
                     // CMP: the pivot row in chunks of PC double2, the next chunk's reads issued before this
                     // chunk's FMAs (the whole row beside Krow does not fit the 3-wave budget)
-                    constexpr int PC = LEAN ? TGMPC_PCH : (CMP && TGMPC_PCH_W2 > 0 ? TGMPC_PCH_W2 : NN / 2 - 1);
+                    constexpr int PC = LEAN ? TGMPC_PCH : (CMP ? TGMPC_PCH_W2 : NN / 2 - 1);
+                    static_assert(PC > 0, "pivot-row chunk");
                     const double2 p0 = prow2[0];
                     double2 pr[PC];
 #pragma unroll
@@ -1783,15 +1556,15 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                     Krow[j] = __hiloint2double(hi, lo);
                     __builtin_amdgcn_sched_barrier(0);   // one register at a time (no batch of 80 temporaries)
                 }
-            } else if constexpr (RECV2) {
-                // Two-wave sweep (capacity 80, one wave per SIMD), ONE fma per entry and pivot: the receiver
+            } else {
+                // Two-wave sweep (capacity 80; the lean two-wave instance too), ONE fma per entry and pivot: the receiver
                 // form of the one-wave sweep above.  Rows start SHIFTED: lane t holds row t - SP2 (SP2 = 128 - NN
                 // spare lanes first, holding exact zero rows).  Pivot pv's new row K_pj / d is formed in
                 // receiver lane pv -- a spare lane while pv < SP2; the lanes SP2..NN-1 held rows 0..NN-SP2-1,
                 // all dropped by pivot NN - SP2 and zeroed then -- so row r ends in lane r: no final
-                // permutation across the waves.  Same values as the two-operation form (see above).
+                // permutation across the waves.  Same values as forming the pivot row in place (see above).
                 constexpr int SB = 2 * NN + 2;
-                static_assert(NN <= 2 * SP2, "receivers: the spare lanes, then the first dropped rows' lanes");
+                static_assert(RECV2 && NN <= 2 * SP2, "receivers: the spare lanes, then the first dropped rows' lanes");
                 int rho = (t >= SP2) ? t - SP2 : -1;   // row held by this lane (-1: zero or dropped)
                 if (rho >= 0) {
                     s_sw[rho] = Krow[0];
@@ -1809,7 +1582,10 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                     const int o = pv & 1;
                     const double* prow = s_sw + o * SB + o + pv;
                     const double2* prow2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(prow, 16));
-                    constexpr int PC = TGMPC_PCH80 > 0 ? TGMPC_PCH80 : 1;
+                    // the pivot row in chunks of PC double2, the next chunk's reads issued before this chunk's FMAs
+                    // (the row of K^-1 and the whole pivot row do not fit 256 registers)
+                    constexpr int PC = L2W ? TGMPC_PCH2 : TGMPC_PCH80;
+                    static_assert(PC > 0, "pivot-row chunk");
                     const double2 p0 = prow2[0];
                     double2 pr[PC];
 #pragma unroll
@@ -1847,97 +1623,6 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                     Krow[0] = n0;
                     Krow[NN - 1] = k0;
                 }
-            } else {
-            {
-                // Pivot pv: K_tj <- K_tj - (K_tp / d) K_pj off the pivot row, K_pj / d on it, column
-                // pv <- K_tp / d (and -1/d on the pivot).  The next pivot's column (new Krow[0]) is
-                // computed and published FIRST, so its LDS write overlaps the remaining FMAs.
-                // Buffers: column published twice (s_sw[o + t], s_sw[o + t + NN]) with o = pv & 1, so
-                // the rotated pivot row s_sw + o + pv starts 16-byte aligned.
-                constexpr int SB = 2 * NN + 2;
-                if (t < NN) {
-                    s_sw[t] = Krow[0];
-                    s_sw[t + NN] = Krow[0];
-                }
-                TGMPC_PRAGMA(unroll TGMPC_SWEEP_UNROLL2)
-                for (int pv = 0; pv < NN; ++pv) {
-                    __syncthreads();
-                    const int o = pv & 1;
-                    const double* prow = s_sw + o * SB + o + pv;
-                    // the rotated pivot row as 20 aligned 16-byte reads, issued ahead of their FMAs
-                    const double2* prow2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(prow, 16));
-                    if constexpr (L2W || (WAVES > 1 && TGMPC_PCH80 > 0)) {
-                        // the pivot row in chunks of PC double2, the next chunk's reads issued before this chunk's
-                        // FMAs (the row of K^-1 and the whole pivot row do not fit 256 registers); same arithmetic
-                        constexpr int PC = L2W ? TGMPC_PCH2 : (TGMPC_PCH80 > 0 ? TGMPC_PCH80 : 1);
-                        const double2 p0 = prow2[0];
-                        double2 pr[PC];
-#pragma unroll
-                        for (int i = 0; i < PC; ++i) if (1 + i < NN / 2) pr[i] = prow2[1 + i];
-                        const double d = p0.x;
-                        ok = ok && (d > 0.0);
-                        const double dinv = rcp_nr(d);
-                        const bool piv = (t == pv);
-                        const double fd = Krow[0] * dinv;
-                        const double al = piv ? 0.0 : 1.0, be = piv ? dinv : -fd;
-                        const double k0 = piv ? -dinv : fd;
-                        const double n0 = fma(be, p0.y, al * Krow[1]);
-                        if (t < NN) {
-                            double* nb = s_sw + (o ^ 1) * SB + (o ^ 1);
-                            nb[t] = n0;
-                            nb[t + NN] = n0;
-                        }
-#pragma unroll
-                        for (int c = 1; c < NN / 2; c += PC) {
-                            double2 pn[PC];
-#pragma unroll
-                            for (int i = 0; i < PC; ++i) if (c + PC + i < NN / 2) pn[i] = prow2[c + PC + i];
-#pragma unroll
-                            for (int i = 0; i < PC; ++i) {
-                                if (c + i < NN / 2) {
-                                    const int j = 2 * (c + i);
-                                    Krow[j - 1] = fma(be, pr[i].x, al * Krow[j]);
-                                    Krow[j] = fma(be, pr[i].y, al * Krow[j + 1]);
-                                }
-                            }
-#pragma unroll
-                            for (int i = 0; i < PC; ++i) pr[i] = pn[i];
-                        }
-                        Krow[0] = n0;
-                        Krow[NN - 1] = k0;
-                        continue;
-                    }
-                    double2 pr[NN / 2];
-#pragma unroll
-                    for (int i = 0; i < NN / 2; ++i) pr[i] = prow2[i];
-                    const double d = pr[0].x;
-                    ok = ok && (d > 0.0);
-                    const double dinv = rcp_nr(d);
-                    const bool piv = (t == pv);
-                    const double fd = Krow[0] * dinv;
-                    // (a single-FMA form with c = 1/d - 1 on the pivot row was measured: no faster --
-                    // the loop is latency-bound -- and it costs polish accuracy at large pivots)
-                    const double al = piv ? 0.0 : 1.0, be = piv ? dinv : -fd;
-                    const double k0 = piv ? -dinv : fd;
-                    const double n0 = fma(be, pr[0].y, al * Krow[1]);
-                    if (t < NN) {
-                        double* nb = s_sw + (o ^ 1) * SB + (o ^ 1);
-                        nb[t] = n0;
-                        nb[t + NN] = n0;
-                    }
-#pragma unroll
-                    for (int j = 2; j < NN; ++j) Krow[j - 1] = fma(be, (j & 1) ? pr[j >> 1].y : pr[j >> 1].x, al * Krow[j]);
-                    // keep ~8 reads in flight ahead of the FMAs (the default schedule waits on each)
-                    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-                    for (int i = 0; i < NN / 2 - 8; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    Krow[0] = n0;
-                    Krow[NN - 1] = k0;   // rotate: the pivot column moves to the end
-                }
-            }
             }
             // (L2W: the pivot columns share the exchange region -- no wave writes an exchange slot before the
             // other has read the last pivot row)
@@ -1947,9 +1632,6 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 for (int j = 0; j < NN; ++j) Krow[j] = -Krow[j];
             }
             toc(cyc_sweep);
-#if TGMPC_PRIO_SWEEP
-            if (FUSED) __builtin_amdgcn_s_setprio(0);
-#endif
             unstash();
             reload();
             if (!ok) {

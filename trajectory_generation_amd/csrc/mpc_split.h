@@ -72,22 +72,9 @@ __device__ __forceinline__ double pair_max(double v) {   // NaN-propagating
 // INLIN (implied by FUSED; the step entry point's default, traj_debug_step_linearize): the same in-workgroup
 // linearization for a step launch -- one launch per call instead of rollout_kernel + jac_kernel + this kernel, the
 // drop-in call's latency; bit-identical to the three-launch sequence.
-#ifndef TGMPC_SPLIT_GHOST
-#define TGMPC_SPLIT_GHOST 1
-#endif
-constexpr bool SPLIT_GHOST = TGMPC_SPLIT_GHOST != 0;
-#ifndef TGMPC_SPLIT_BLOCK
-// pivots per sweep round: 2 (one LDS round and one barrier per pair; the default) or 1 (the single sweep).  A 4-pivot
-// form (a per-lane LDL' solve of the block) measured 1.34-1.37 M against 1.42 M at config 3 and moved one capped
-// instance's status in test_config3_iteration_cap_steps_vs_oracle; it is not kept
-#define TGMPC_SPLIT_BLOCK 2
-#endif
-constexpr int SPLIT_BLOCK = TGMPC_SPLIT_BLOCK;
-constexpr bool SPLIT_BLOCK2 = SPLIT_BLOCK == 2;
-static_assert(SPLIT_BLOCK == 1 || SPLIT_BLOCK == 2, "sweep block");
-#ifndef TGMPC_SPLIT_NOZERO_TIMING
-#define TGMPC_SPLIT_NOZERO_TIMING 0   // 1: timing experiment only (wrong results): the pivot rows are not zeroed
-#endif
+// The sweep takes 2 pivots per round (one LDS round and one barrier per pair).  A 4-pivot form (a per-lane LDL' solve of
+// the block) measured 1.34-1.37 M against 1.42 M at config 3 and moved one capped instance's status in
+// test_config3_iteration_cap_steps_vs_oracle; it is not kept
 // DIAG (fused only, when a diagnostic buffer is set: traj_debug_set_stamps): per-phase s_memtime stamps of each
 // instance's last step in a.dbg[b][0..11] (tools/split_phase.py); the production instances compile none of it.
 template <int H, bool CLOSED = false, bool FUSED = false, bool INLIN = FUSED, bool DIAG = false>
@@ -98,14 +85,13 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
     using SC = SplitCfg<H>;
     constexpr int NR = SC::NR, NT = SC::NT, NRW = SC::NRW, WAVES = SC::WAVES;
     constexpr int PL = 2 * H;                 // P row stride (doubles)
-    constexpr int SPV = 2 * H + 2;            // one pivot-row slice buffer: [off + m], m < 2H, off in {0, 1}
+    constexpr int SPV = 2 * H + 2;            // one pivot-row slice buffer: [m], m < 2H (2 spare)
     __shared__ __attribute__((aligned(16))) double s_bc[2][NRW];       // broadcast vectors (rotating)
     __shared__ double s_ex[4][NRW];                                    // +-2 exchanges (rotating)
     // ADMM: every row's constants of the rate-row update, read by the row two below it (the ghost update, below)
-    __shared__ __attribute__((aligned(16))) double s_gh[SPLIT_GHOST ? NRW + 2 : 1][6];
-    __shared__ __attribute__((aligned(16))) double s_pv[SPLIT_BLOCK > 1 ? 1 : 2][2][SPV];   // sweep: [parity][half][slice]
+    __shared__ __attribute__((aligned(16))) double s_gh[NRW + 2][6];
     // block sweep: [parity][column of the block][half][slice]
-    __shared__ __attribute__((aligned(16))) double s_pv2[SPLIT_BLOCK2 ? 2 : 1][SPLIT_BLOCK2 ? 2 : 1][2][SPV];
+    __shared__ __attribute__((aligned(16))) double s_pv2[2][2][2][SPV];
     __shared__ double s_red[WAVES * 8];
     __shared__ int s_flag[4];
     __shared__ double s_xc[CLOSED || INLIN ? 6 : 1], s_uc[CLOSED || INLIN ? 2 : 1];
@@ -698,7 +684,7 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
             if (w1 != 0.0) rho = fmin(fmax(w0, RHO_MIN), RHO_MAX);
         }
         double x = 0.0, zb = 0.0, zr = 0.0, yb = 0.0, yr = 0.0;
-        double zr_g = 0.0, yr_g = 0.0;   // the ghost of row r + 2's rate-row state (SPLIT_GHOST)
+        double zr_g = 0.0, yr_g = 0.0;   // the ghost of row r + 2's rate-row state (the ghost update, below)
         double rb = rho_for(slb, sub, rho), rr = rho_for(slr, sur, rho);
         Res rs0 = {0, 0, 0, 0, 0, 0, 0, 0};
         int rounds = 0, ps = 0, actb = 0, actr = 0;
@@ -729,7 +715,7 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
                 double* const prow = Prow(r);
                 double o_dg = 0.0, o_sp = 0.0, o_sm = 0.0;
                 const bool has_sp = own && r + 2 < n, has_sm = own && has_prev;
-                if (SPLIT_GHOST && phase == PH_ADMM && h == 0) {   // this row's constants for the ghost update
+                if (phase == PH_ADMM && h == 0) {   // this row's constants for the ghost update
                     double* g = s_gh[r];
                     g[0] = a_r; g[1] = a_rm; g[2] = slr; g[3] = sur; g[4] = rr; g[5] = 1.0 / rr;
                 }
@@ -760,143 +746,72 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
             // its rotated pivot-row entries from one 16-byte aligned slice.  Pivots past n (padding) only rotate.
             bool ok = true;
             [[maybe_unused]] const long long t_sw = DIAG ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            // SPLIT_BLOCK2: pivots p, p + 1 (q even, both in half hp: H and n are even) as one 2 x 2 block -- the
-            // composition of the two single sweeps, with the second pivot's d and every coefficient formed as the
-            // sequential sweep forms them (a = K_pp, b = K_p+1,p, c = K_p+1,p+1; 1/a; d2 = c - (b/a) b; 1/d2):
+            // Pivots p, p + 1 (q even, both in half hp: H and n are even) go as one 2 x 2 block -- the composition of
+            // the two single-pivot sweeps, with the second pivot's d and every coefficient formed as the sequential
+            // sweep forms them (a = K_pp, b = K_p+1,p, c = K_p+1,p+1; 1/a; d2 = c - (b/a) b; 1/d2):
             //   row r outside the block: u = K_rp, v = K_r,p+1; beta = (v - (u/a) b)/d2, alpha = (u - beta b)/a;
             //     K_rj <- K_rj - alpha K_pj - beta K_p+1,j, and (K_rp, K_r,p+1) <- (alpha, beta);
             //   rows p, p + 1: the rows of the block inverse G (g00 = 1/a + (b/a)^2/d2, g01 = g10 = -(b/a)/d2,
             //     g11 = 1/d2) times the pivot rows, from an exact zero row, and (K_pp .. ) <- -G.
             // The two pivot columns are published as two slices (A: column p, B: column p + 1) in the rotated layout
-            // of the single sweep; registers rotate by two per block.  The same algebra as two single pivots, one
+            // above; registers rotate by two per block.  The same algebra as two single pivots, one
             // barrier and one LDS round instead of two; the rounding of the composed coefficients differs in the
             // last bits from the sequential form.
-            if constexpr (SPLIT_BLOCK2) {
-                for (int hp = 0; hp < 2; ++hp) {
-#pragma unroll 2
-                    for (int q = 0; q < H; q += 2) {
-                        const int pv = hp * H + q;
-                        if (pv >= n) {   // a padding pair: identity rows, a rotation by two only
-                            const double k0 = Kh[0], k1 = Kh[1];
-#pragma unroll
-                            for (int i = 2; i < H; ++i) Kh[i - 2] = Kh[i];
-                            Kh[H - 2] = k0;
-                            Kh[H - 1] = k1;
-                            continue;
-                        }
-                        double e0, e1, f0, f1;
-                        swap32(Kh[0], e0, e1);
-                        swap32(Kh[1], f0, f1);
-                        const double u = hp ? e1 : e0;   // K[r][p]
-                        const double v = hp ? f1 : f0;   // K[r][p + 1]
-                        const int par = (pv >> 1) & 1;
-                        double* const slA = &s_pv2[par][0][0][0];
-                        double* const slB = &s_pv2[par][1][0][0];
-                        if (r < NR) {
-                            slA[(r / H) * SPV + (r % H) + h * H] = u;
-                            slB[(r / H) * SPV + (r % H) + h * H] = v;
-                        }
-                        [[maybe_unused]] long long ts0 = 0;
-                        if constexpr (DIAG) ts0 = __builtin_amdgcn_s_memtime();
-                        __syncthreads();
-                        if constexpr (DIAG) cyc_swb += (long long)__builtin_amdgcn_s_memtime() - ts0;
-                        const double2 ab = *reinterpret_cast<const double2*>(&slA[hp * SPV + q]);   // K_pp, K_p+1,p
-                        const double cc = slB[hp * SPV + q + 1];                                     // K_p+1,p+1
-                        // the pivot rows' entries of this half, rotated: K[p | p + 1][h H + (i + q) mod H]
-                        const double2* pa2 =
-                            reinterpret_cast<const double2*>(__builtin_assume_aligned(slA + h * SPV + q, 16));
-                        const double2* pb2 =
-                            reinterpret_cast<const double2*>(__builtin_assume_aligned(slB + h * SPV + q, 16));
-                        double2 ca[2], cb[2];
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            ca[i] = pa2[i];
-                            cb[i] = pb2[i];
-                        }
-                        const double a = ab.x, bb = ab.y;
-                        const double ainv = rcp_nr(a);
-                        const double t = bb * ainv;
-                        const double d2 = fma(-t, bb, cc);
-                        ok = ok && (a > 0.0) && (d2 > 0.0);
-                        const double d2inv = rcp_nr(d2);
-                        const bool p0 = (r == pv), p1 = (r == pv + 1);
-                        const double td = t * d2inv;
-                        const double beta = fma(-(u * ainv), bb, v) * d2inv;
-                        const double alpha = fma(-beta, bb, u) * ainv;
-                        // coefficients of the two pivot rows: -(alpha, beta) outside the block, G's row inside
-                        const double cA = p0 ? fma(td, t, ainv) : (p1 ? -td : -alpha);
-                        const double cB = p0 ? -td : (p1 ? d2inv : -beta);
-                        if ((p0 || p1) && !TGMPC_SPLIT_NOZERO_TIMING) {
-#pragma unroll
-                            for (int i = 0; i < H; ++i) Kh[i] = 0.0;
-                        }
-                        [[maybe_unused]] long long ts2 = 0;
-                        if constexpr (DIAG) {
-                            ts2 = __builtin_amdgcn_s_memtime();
-                            cyc_sw1 += ts2 - ts0;
-                        }
-                        // old registers 0, 1 (the pivot columns in half hp, ordinary columns in the other half)
-                        const double w0 = fma3(cA, ca[0].x, fma(cB, cb[0].x, Kh[0]));
-                        const double w1 = fma3(cA, ca[0].y, fma(cB, cb[0].y, Kh[1]));
-                        Kh[0] = fma3(cA, ca[1].x, fma(cB, cb[1].x, Kh[2]));
-                        Kh[1] = fma3(cA, ca[1].y, fma(cB, cb[1].y, Kh[3]));
-#pragma unroll
-                        for (int c4 = 4; c4 < H; c4 += 4) {   // columns c4 .. c4 + 3 (double2 c4 / 2, c4 / 2 + 1)
-#pragma unroll
-                            for (int i = 0; i < 2; ++i) {
-                                ca[i] = pa2[c4 / 2 + i];
-                                cb[i] = pb2[c4 / 2 + i];
-                            }
-#pragma unroll
-                            for (int i = 0; i < 2; ++i) {
-                                const int j = c4 + 2 * i;
-                                Kh[j - 2] = fma3(cA, ca[i].x, fma(cB, cb[i].x, Kh[j]));
-                                Kh[j - 1] = fma3(cA, ca[i].y, fma(cB, cb[i].y, Kh[j + 1]));
-                            }
-                        }
-                        Kh[H - 2] = (h == hp) ? -cA : w0;
-                        Kh[H - 1] = (h == hp) ? -cB : w1;
-                        if constexpr (DIAG) cyc_sw2 += (long long)__builtin_amdgcn_s_memtime() - ts2;
-                    }
-                }
-            } else
             for (int hp = 0; hp < 2; ++hp) {
 #pragma unroll 2
-                for (int q = 0; q < H; ++q) {
+                for (int q = 0; q < H; q += 2) {
                     const int pv = hp * H + q;
-                    if (pv >= n) {   // padding pivot: the identity row, a rotation only
-                        const double k0 = Kh[0];
+                    if (pv >= n) {   // a padding pair: identity rows, a rotation by two only
+                        const double k0 = Kh[0], k1 = Kh[1];
 #pragma unroll
-                        for (int i = 1; i < H; ++i) Kh[i - 1] = Kh[i];
-                        Kh[H - 1] = k0;
+                        for (int i = 2; i < H; ++i) Kh[i - 2] = Kh[i];
+                        Kh[H - 2] = k0;
+                        Kh[H - 1] = k1;
                         continue;
                     }
-                    double e0, e1;
+                    double e0, e1, f0, f1;
                     swap32(Kh[0], e0, e1);
-                    const double kp = hp ? e1 : e0;            // K[r][p]: register 0 of the half holding column p
-                    const int par = pv & 1, off = q & 1;
-                    double* const sl = &s_pv[par][0][0];
-                    // row r publishes its K[r][p] = K[p][r] at slice position (r mod H) and (r mod H) + H of half r / H
-                    if (r < NR) sl[(r / H) * SPV + off + (r % H) + h * H] = kp;
+                    swap32(Kh[1], f0, f1);
+                    const double u = hp ? e1 : e0;   // K[r][p]
+                    const double v = hp ? f1 : f0;   // K[r][p + 1]
+                    const int par = (pv >> 1) & 1;
+                    double* const slA = &s_pv2[par][0][0][0];
+                    double* const slB = &s_pv2[par][1][0][0];
+                    if (r < NR) {
+                        slA[(r / H) * SPV + (r % H) + h * H] = u;
+                        slB[(r / H) * SPV + (r % H) + h * H] = v;
+                    }
                     [[maybe_unused]] long long ts0 = 0;
                     if constexpr (DIAG) ts0 = __builtin_amdgcn_s_memtime();
                     __syncthreads();
                     if constexpr (DIAG) cyc_swb += (long long)__builtin_amdgcn_s_memtime() - ts0;
-                    const double d = sl[hp * SPV + off + q];
-                    // rotated pivot-row entries of this half: K[p][h H + (i + q) mod H] at sl[h SPV + off + q + i] --
-                    // the first chunk read with d, ahead of the reciprocal and the pivot row's branch
-                    const double2* pr2 =
-                        reinterpret_cast<const double2*>(__builtin_assume_aligned(sl + h * SPV + off + q, 16));
-                    double2 cur[4];
+                    const double2 ab = *reinterpret_cast<const double2*>(&slA[hp * SPV + q]);   // K_pp, K_p+1,p
+                    const double cc = slB[hp * SPV + q + 1];                                     // K_p+1,p+1
+                    // the pivot rows' entries of this half, rotated: K[p | p + 1][h H + (i + q) mod H]
+                    const double2* pa2 =
+                        reinterpret_cast<const double2*>(__builtin_assume_aligned(slA + h * SPV + q, 16));
+                    const double2* pb2 =
+                        reinterpret_cast<const double2*>(__builtin_assume_aligned(slB + h * SPV + q, 16));
+                    double2 ca[2], cb[2];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) cur[i] = pr2[i];
-                    ok = ok && (d > 0.0);
-                    const double dinv = rcp_nr(d);
-                    const bool piv = (r == pv);
-                    const double fd = kp * dinv;
-                    const double be = piv ? dinv : -fd;
-                    const double k0 = piv ? -dinv : fd;
-                    if (piv && !TGMPC_SPLIT_NOZERO_TIMING) {   // the pivot row becomes K_pj / d: an exact zero row plus be * K_pj
+                    for (int i = 0; i < 2; ++i) {
+                        ca[i] = pa2[i];
+                        cb[i] = pb2[i];
+                    }
+                    const double a = ab.x, bb = ab.y;
+                    const double ainv = rcp_nr(a);
+                    const double t = bb * ainv;
+                    const double d2 = fma(-t, bb, cc);
+                    ok = ok && (a > 0.0) && (d2 > 0.0);
+                    const double d2inv = rcp_nr(d2);
+                    const bool p0 = (r == pv), p1 = (r == pv + 1);
+                    const double td = t * d2inv;
+                    const double beta = fma(-(u * ainv), bb, v) * d2inv;
+                    const double alpha = fma(-beta, bb, u) * ainv;
+                    // coefficients of the two pivot rows: -(alpha, beta) outside the block, G's row inside
+                    const double cA = p0 ? fma(td, t, ainv) : (p1 ? -td : -alpha);
+                    const double cB = p0 ? -td : (p1 ? d2inv : -beta);
+                    if (p0 || p1) {
 #pragma unroll
                         for (int i = 0; i < H; ++i) Kh[i] = 0.0;
                     }
@@ -905,27 +820,27 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
                         ts2 = __builtin_amdgcn_s_memtime();
                         cyc_sw1 += ts2 - ts0;
                     }
-                    const double last = fma3(be, cur[0].x, Kh[0]);   // column h H + q (the non-pivot half's entry)
+                    // old registers 0, 1 (the pivot columns in half hp, ordinary columns in the other half)
+                    const double w0 = fma3(cA, ca[0].x, fma(cB, cb[0].x, Kh[0]));
+                    const double w1 = fma3(cA, ca[0].y, fma(cB, cb[0].y, Kh[1]));
+                    Kh[0] = fma3(cA, ca[1].x, fma(cB, cb[1].x, Kh[2]));
+                    Kh[1] = fma3(cA, ca[1].y, fma(cB, cb[1].y, Kh[3]));
 #pragma unroll
-                    for (int i0 = 0; i0 < H; i0 += 8) {
-                        double2 nxt[4];
-                        if (i0 + 8 < H) {
+                    for (int c4 = 4; c4 < H; c4 += 4) {   // columns c4 .. c4 + 3 (double2 c4 / 2, c4 / 2 + 1)
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) nxt[i] = pr2[(i0 + 8) / 2 + i];
+                        for (int i = 0; i < 2; ++i) {
+                            ca[i] = pa2[c4 / 2 + i];
+                            cb[i] = pb2[c4 / 2 + i];
                         }
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int j = i0 + 2 * i;
-                            // (three-address fma: the rotated destination is written directly, no register copies)
-                            if (j > 0) Kh[j - 1] = fma3(be, cur[i].x, Kh[j]);
-                            Kh[j] = fma3(be, cur[i].y, Kh[j + 1]);
-                        }
-                        if (i0 + 8 < H) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+                        for (int i = 0; i < 2; ++i) {
+                            const int j = c4 + 2 * i;
+                            Kh[j - 2] = fma3(cA, ca[i].x, fma(cB, cb[i].x, Kh[j]));
+                            Kh[j - 1] = fma3(cA, ca[i].y, fma(cB, cb[i].y, Kh[j + 1]));
                         }
                     }
-                    Kh[H - 1] = (h == hp) ? k0 : last;
+                    Kh[H - 2] = (h == hp) ? -cA : w0;
+                    Kh[H - 1] = (h == hp) ? -cB : w1;
                     if constexpr (DIAG) cyc_sw2 += (long long)__builtin_amdgcn_s_memtime() - ts2;
                 }
             }
@@ -953,40 +868,29 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
                 int chk = c.check_interval - (iter - 1) % c.check_interval;
                 const double oma = 1.0 - alpha;
                 const double rib = 1.0 / rb, rir = 1.0 / rr;
-                // SPLIT_GHOST: row r also runs row r + 2's rate-row update (zr, yr: the same operations on the same
+                // The ghost update: row r also runs row r + 2's rate-row update (zr, yr: the same operations on the same
                 // values, so the same bits), which is all that A' w needs of row r + 2 -- so the iteration exchanges
                 // only xt (both neighbours in one round) and has two barriers (the broadcast, the exchange), not three.
                 const double2* const gq = reinterpret_cast<const double2*>(s_gh[r + 2]);
                 const bool has_up = own && r + 2 < n;
                 for (; iter <= c.max_iter; ++iter) {
                     const double wb = fma(rb, zb, -yb), wr = fma(rr, zr, -yr);
-                    double rp_up;
-                    double2 g01, g23, g45;
-                    if constexpr (SPLIT_GHOST) {
-                        g01 = gq[0]; g23 = gq[1]; g45 = gq[2];   // a_r, a_rm | slr, sur | rr, 1 / rr of row r + 2
-                        rp_up = has_up ? g01.y * fma(g45.x, zr_g, -yr_g) : 0.0;
-                    } else {
-                        rp_up = exch(a_rm * wr, +2);
-                    }
+                    const double2 g01 = gq[0], g23 = gq[1], g45 = gq[2];   // a_r, a_rm | slr, sur | rr, 1 / rr of row r + 2
+                    const double rp_up = has_up ? g01.y * fma(g45.x, zr_g, -yr_g) : 0.0;
                     const double atw = fma(a_b, wb, fma(a_r, wr, -rp_up));
                     const double xt = Kmul(fma(sig, x, atw - qi));
-                    double xt_dn;
-                    if constexpr (SPLIT_GHOST) {
-                        double* buf = s_ex[xb & 3];
-                        xb++;
-                        if (h == 0) buf[r] = xt;
-                        __syncthreads();
-                        xt_dn = (own && r >= 2) ? buf[r - 2] : 0.0;
-                        const double xt_up = has_up ? buf[r + 2] : 0.0;
-                        // row r + 2's update (its xt_dn is this row's xt)
-                        const double ztr_g = fma(g01.x, xt_up, -(g01.y * xt));
-                        const double zrr_g = fma(alpha, ztr_g, oma * zr_g);
-                        const double nzr_g = clamp_mm(fma(g45.y, yr_g, zrr_g), g23.x, g23.y);
-                        yr_g = fma(g45.x, zrr_g - nzr_g, yr_g);
-                        zr_g = nzr_g;
-                    } else {
-                        xt_dn = exch(xt, -2);
-                    }
+                    double* buf = s_ex[xb & 3];
+                    xb++;
+                    if (h == 0) buf[r] = xt;
+                    __syncthreads();
+                    const double xt_dn = (own && r >= 2) ? buf[r - 2] : 0.0;
+                    const double xt_up = has_up ? buf[r + 2] : 0.0;
+                    // row r + 2's update (its xt_dn is this row's xt)
+                    const double ztr_g = fma(g01.x, xt_up, -(g01.y * xt));
+                    const double zrr_g = fma(alpha, ztr_g, oma * zr_g);
+                    const double nzr_g = clamp_mm(fma(g45.y, yr_g, zrr_g), g23.x, g23.y);
+                    yr_g = fma(g45.x, zrr_g - nzr_g, yr_g);
+                    zr_g = nzr_g;
                     const double ztb = a_b * xt, ztr = fma(a_r, xt, -(a_rm * xt_dn));
                     const double xn = fma(alpha, xt, oma * x);
                     const double zrb = fma(alpha, ztb, oma * zb), zrr = fma(alpha, ztr, oma * zr);

@@ -167,15 +167,8 @@ __global__ __launch_bounds__(1024) void order_kernel(const double* warm, int B, 
 // capacity 80: a one-wave capacity-64 instance has no spare lanes for the receiver sweep and, at 64 doubles of K^-1
 // per lane beside the chunked reads, spilled 780-830 B/lane at 512 registers; measured at B = 1024
 // (profiles/r05_tiers.json) it ran N = 24 / 30 / 32 at 0.43 / 0.34 / 0.35 M steps/s against 0.56 / 0.47 / 0.46 M on
-// capacity 80, so it is not built (TGMPC_CAP64=1 brings it back for experiments)
-#ifndef TGMPC_CAP64
-#define TGMPC_CAP64 0
-#endif
-#if TGMPC_CAP64
-#define TGMPC_CAPACITIES(X) X(16) X(32) X(40) X(64) X(80)
-#else
+// capacity 80, so there is none
 #define TGMPC_CAPACITIES(X) X(16) X(32) X(40) X(80)
-#endif
 #define TGMPC_DECL(NNV) int launch_mpc_##NNV(const KArgs& a, hipStream_t st, int mode);
 TGMPC_CAPACITIES(TGMPC_DECL)
 #undef TGMPC_DECL
@@ -826,9 +819,9 @@ int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c,
     // kernel instance: capacity 40, 2 waves per SIMD (3 from TRAJ_FUSED_W3_MIN_STEPS steps when that is set); capacity
     // 80, one wave per SIMD (the lean two-wave instance, traj_debug_fused_waves(2), spills at its 256 registers)
     constexpr int w3_min = TRAJ_FUSED_W3_MIN_STEPS;
-    // (by the capacity launch_mpc picks: n = 2N > 40 runs capacity 80 -- 64 only in a TGMPC_CAP64 build, whose fused
-    // launch ignores wps -- so 20 < N <= 32 takes the one-wave-per-SIMD instance too; until round 5 it fell through
-    // to the opt-in lean two-wave instance, which spills: N = 30 ran 0.68 M against N = 40's 0.99 M)
+    // (by the capacity launch_mpc picks: n = 2N > 40 runs capacity 80, so 20 < N <= 32 takes the one-wave-per-SIMD
+    // instance too; until round 5 it fell through to the opt-in lean two-wave instance, which spills: N = 30 ran
+    // 0.68 M against N = 40's 0.99 M)
     a.wps = g_fused_waves ? g_fused_waves : (2 * c->N > 40 ? 1 : ((w3_min > 0 && steps >= w3_min) ? 3 : 2));
     a.spin_limit = g_spin_limit;
     a.dbg_items = g_dbg_items;
