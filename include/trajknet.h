@@ -14,6 +14,8 @@
  *   kalman_net.py:145-216 whole step (throughput path)     traj_knet_front_f32 + traj_knet_fc2_f32 + traj_knet_back_f32
  *   test_prediction.py:67-112,198-221 sliding-window        traj_knet_rollout_eval_f32
  *     open-loop rollout + ADE / FDE
+ *   pipeline_prediction.py:45-99 prediction loss of         traj_knet_pred_loss_f32 (+ its gradient w.r.t. the
+ *     training (H-step rollout from every posterior)          posteriors)
  *   (no reference counterpart) EKF baseline of config 5     traj_ekf_run_f64
  *
  * Conventions as trajmpc.h: device pointers, row-major, asynchronous on `stream`, 0 / TRAJ_E_*.
@@ -144,6 +146,27 @@ int traj_knet_rollout_eval_f32(const traj_vehicle_params* p, const traj_knet_lim
                                int H, int t0, int step, int nwin, const float* x_est, int e_sb, int e_sc, int e_st,
                                const float* x_mean, const float* x_std, const float* u, const float* x_gt, float* ade,
                                float* fde, float* err_profile, float* pred, void* stream);
+
+/* Open-loop prediction loss of training (pipeline_prediction.py:61-99 compute_prediction_loss with
+ * _compute_step_loss_real :45-59) and its gradient, all windows of B sequences in one launch.
+ * Window w of sequence b starts at t = t0 + w * step (w < nwin, t <= T - 1) from x_est[b*e_sb + c*e_sc + w*e_sw]:
+ * x_est is indexed by WINDOW (a stacked TBPTT chunk [B,6,K]: t0 = the chunk's first step, step = 1, strides
+ * 6K, K, 1; a [B,6,T] estimate tensor: the pointer of column t0 with strides 6T, T, step).
+ *   x_0    = x_est * x_std + x_mean                                  (x_mean / x_std [6])
+ *   x_k    = clamp(x_k-1 + Ts f(x_k-1, u_real[b, :, t + k - 1])),  k = 1 .. valid = max(0, min(H, T - 1 - t)),
+ *            u_real = u * u_std + u_mean (u_mean / u_std [2]; both NULL: u [B,2,T] is already real)
+ *   e_k    = x_k - (x_gt_norm[b, :, t + k] * x_std + x_mean), phi as atan2(sin, cos) of the difference
+ *   part[b*nwin + w]          = sum_k sum_c e_k,c^2 / (6 valid)     (the mean over b is the reference's loss at t)
+ *   grad[(b*6 + c)*nwin + w]  = d part[b, w] / d x_est[b, c, w]     (written when grad != NULL; part is the same
+ *            bits either way): the derivative torch's autograd gives for the expressions above -- clamp passes the
+ *            gradient on the closed interval, abs'(0) = 0, max(|vx|, vx_zero) halves a tie, the wrapped
+ *            difference has derivative 1 -- carried forward with the rollout as d x_k / d x_0.
+ * valid = 0: part = 0 and grad = 0.  Deterministic (one thread per window, sums in a fixed order).
+ * TRAJ_E_ARG for H < 1, step < 1, a window starting past T - 1, negative strides or a missing pointer. */
+int traj_knet_pred_loss_f32(const traj_vehicle_params* p, const traj_knet_limits* lim, float Ts, int B, int T, int H,
+                            int t0, int step, int nwin, const float* x_est, int e_sb, int e_sc, int e_sw,
+                            const float* x_mean, const float* x_std, const float* u_mean, const float* u_std,
+                            const float* u, const float* x_gt_norm, float* part, float* grad, void* stream);
 
 /* Build-defined EKF baseline for config 5 ("MSE vs reference EKF"; the reference has no EKF, SURVEY.md
  * 8(f) f2), float64, one thread per sequence, all T steps in one launch:

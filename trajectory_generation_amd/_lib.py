@@ -178,6 +178,9 @@ _SIGS = {
     "traj_knet_rollout_eval_f32": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_float, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _V, C.c_int, C.c_int, C.c_int,
                                              _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_knet_pred_loss_f32": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_float, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _V, C.c_int, C.c_int, C.c_int,
+                                          _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "traj_ekf_run_f64": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_double, C.c_int, C.c_int,
                                    _V, _V, _V, _V, _V, _V, _V, _V]),
     "traj_gen_abi_version": (C.c_int, []),

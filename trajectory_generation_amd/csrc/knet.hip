@@ -24,9 +24,22 @@ struct KP {   // vehicle parameters rounded to float32
     float Cm1, Cm2, Cr0, Cr2, Br, Cr, Dr, Bf, Cf, Df, m, Iz, lf, lr, maxAlpha, vx_zero;
 };
 
-// VehicleModel.f (vehicle_model.py:109-134) on one real state: xn = clamp(x + Ts f_cont(x, u))
-__device__ __forceinline__ void veh_step(const KP& p, const traj_knet_limits& L, float Ts, const float* x, float d,
-                                         float delta, float* xn) {
+// torch.clamp's backward mask: the gradient passes on the closed interval [lo, hi]
+__device__ __forceinline__ float inside_(float x, float lo, float hi) { return (x >= lo && x <= hi) ? 1.0f : 0.0f; }
+
+// d xn / d x of one veh_step, as torch's autograd differentiates vehicle_model.py:19-79,109-134 (clamp passes the
+// gradient on the closed interval, abs'(0) = 0, max(|vx|, vx_zero) splits a tie in half):
+//   d xn_i / d x_j = post[i] * ((i == j) + Ts * A[i][j - 2])   (A = 0 for j < 2: X and Y enter no derivative)
+struct VehJac {
+    float A[6][4];   // d xdot_i / d (phi, vx, vy, omega), the masks of the four pre-clamps included
+    float post[6];   // masks of the six clamps after the Euler step
+};
+
+// VehicleModel.f (vehicle_model.py:109-134) on one real state: xn = clamp(x + Ts f_cont(x, u)); JAC: also its
+// Jacobian (the forward value is the same expressions either way, bit for bit)
+template <bool JAC>
+__device__ __forceinline__ void veh_step_t(const KP& p, const traj_knet_limits& L, float Ts, const float* x, float d,
+                                           float delta, float* xn, VehJac* J) {
     // pt_f_cont (vehicle_model.py:45-79)
     const float phi = clampf_(x[2], L.phi_min, L.phi_max);
     const float vx = clampf_(x[3], L.vx_min, L.vx_max);
@@ -54,7 +67,50 @@ __device__ __forceinline__ void veh_step(const KP& p, const traj_knet_limits& L,
     const float lo[6] = {L.x_min, L.y_min, L.phi_min, L.vx_min, L.vy_min, L.omega_min};
     const float hi[6] = {L.x_max, L.y_max, L.phi_max, L.vx_max, L.vy_max, L.omega_max};
 #pragma unroll
-    for (int i = 0; i < 6; ++i) xn[i] = clampf_(__fadd_rn(x[i], __fmul_rn(Ts, xd[i])), lo[i], hi[i]);
+    for (int i = 0; i < 6; ++i) {
+        const float raw = __fadd_rn(x[i], __fmul_rn(Ts, xd[i]));
+        xn[i] = clampf_(raw, lo[i], hi[i]);
+        if constexpr (JAC) J->post[i] = inside_(raw, lo[i], hi[i]);
+    }
+    if constexpr (JAC) {
+        const float m_phi = inside_(x[2], L.phi_min, L.phi_max), m_vx = inside_(x[3], L.vx_min, L.vx_max);
+        const float m_vy = inside_(x[4], L.vy_min, L.vy_max), m_om = inside_(x[5], L.omega_min, L.omega_max);
+        // vx_eff = max(|vx|, vx_zero) w.r.t. the clamped vx
+        const float sg = vx > 0.0f ? 1.0f : (vx < 0.0f ? -1.0f : 0.0f);
+        const float ve_vx = (avx > p.vx_zero ? 1.0f : (avx == p.vx_zero ? 0.5f : 0.0f)) * sg;
+        // alpha_f (before its clamp) = -atan2(a1, vx_eff) + delta, alpha_r = atan2(a2, vx_eff)
+        const float a1 = __fadd_rn(__fmul_rn(om, p.lf), vy), a2 = __fsub_rn(__fmul_rn(om, p.lr), vy);
+        const float af_raw = __fadd_rn(-atan2f(a1, vx_eff), delta);
+        const float r1 = fmaf(vx_eff, vx_eff, a1 * a1), r2 = fmaf(vx_eff, vx_eff, a2 * a2);
+        const float af_a1 = -vx_eff / r1, af_ve = a1 / r1, ar_a2 = vx_eff / r2, ar_ve = -a2 / r2;
+        // Fy = D sin(C atan(B alpha))
+        const float qf = __fmul_rn(p.Bf, alpha_f), qr = __fmul_rn(p.Br, alpha_r);
+        const float Ff = p.Df * cosf(__fmul_rn(p.Cf, atanf(qf))) * (p.Cf * p.Bf) / fmaf(qf, qf, 1.0f) *
+                         inside_(af_raw, -p.maxAlpha, p.maxAlpha);               // d Fy_f / d alpha_f (raw)
+        const float Fr = p.Dr * cosf(__fmul_rn(p.Cr, atanf(qr))) * (p.Cr * p.Br) / fmaf(qr, qr, 1.0f);
+        const float Ff_vx = Ff * af_ve * ve_vx, Ff_vy = Ff * af_a1, Ff_om = Ff_vy * p.lf;
+        const float Fr_vx = Fr * ar_ve * ve_vx, Fr_vy = -(Fr * ar_a2), Fr_om = Fr * ar_a2 * p.lr;
+        const float Fx_vx = (-(p.Cm2 * d) - 2.0f * p.Cr2 * vx_eff) * ve_vx;      // d Frx / d vx
+        const float im = 1.0f / p.m, iz = 1.0f / p.Iz, lc = p.lf * cdl;
+        const float A[6][4] = {
+            {-xd[1], cphi, -sphi, 0.0f},
+            {xd[0], sphi, cphi, 0.0f},
+            {0.0f, 0.0f, 0.0f, 1.0f},
+            {0.0f, (Fx_vx - Ff_vx * sdl) * im, om - Ff_vy * sdl * im, vy - Ff_om * sdl * im},
+            {0.0f, (Fr_vx + Ff_vx * cdl) * im - om, (Fr_vy + Ff_vy * cdl) * im, (Fr_om + Ff_om * cdl) * im - vx},
+            {0.0f, (Ff_vx * lc - Fr_vx * p.lr) * iz, (Ff_vy * lc - Fr_vy * p.lr) * iz,
+             (Ff_om * lc - Fr_om * p.lr) * iz}};
+        const float pre[4] = {m_phi, m_vx, m_vy, m_om};
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) J->A[i][c] = A[i][c] * pre[c];
+    }
+}
+
+__device__ __forceinline__ void veh_step(const KP& p, const traj_knet_limits& L, float Ts, const float* x, float d,
+                                         float delta, float* xn) {
+    veh_step_t<false>(p, L, Ts, x, d, delta, xn, nullptr);
 }
 
 // kalman_net.py:145-162 for one sequence: x_post (normalized) -> prior (normalized), m1y, dy = y - m1y
@@ -189,6 +245,113 @@ __global__ __launch_bounds__(64) void knet_rollout_kernel(KP p, traj_knet_limits
     if (gb) {
         ade[i] = (float)(sum / (double)H);   // err_dist.mean()
         fde[i] = e;                          // err_dist[0, -1]
+    }
+}
+
+// pipeline_prediction.py:61-99 (compute_prediction_loss, with _compute_step_loss_real :45-59) for every (sequence b,
+// window w) at once, with the derivative its autograd gives.  Window w starts at t = t0 + w * step from
+// x_est[b, :, w] (indexed by window), rolls the physics valid = max(0, min(H, T - 1 - t)) steps and sums the squared
+// error against the denormalized ground truth, phi as the wrapped difference (derivative 1):
+//   part[b, w] = sum_k sum_c e^2 / (6 valid),   grad[b, :, w] = d part[b, w] / d x_est[b, :, w].
+// The gradient rides forward with the rollout as the sensitivity S = d x_k / d x_0 (no stored states): X and Y enter
+// no derivative, so S is the two scalars d X_k / d X_0, d Y_k / d Y_0 and the 6 x 4 block of columns phi .. omega.
+// One thread per window; every sum runs in a fixed order (k, then c).
+__global__ __launch_bounds__(64) void knet_pred_loss_kernel(KP p, traj_knet_limits L, float Ts, int B, int T, int H,
+                                                            int t0, int step, int nwin, const float* __restrict__ xe,
+                                                            int e_sb, int e_sc, int e_sw,
+                                                            const float* __restrict__ xm, const float* __restrict__ xs,
+                                                            const float* __restrict__ um, const float* __restrict__ us,
+                                                            const float* __restrict__ u, const float* __restrict__ xg,
+                                                            float* __restrict__ part, float* __restrict__ grad) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= B * nwin) return;
+    const int b = i / nwin, w = i - b * nwin, t = t0 + w * step;
+    const int valid = max(0, min(H, T - 1 - t));
+    const float* eb = xe + (size_t)b * e_sb + (size_t)w * e_sw;
+    const float* ub = u + (size_t)b * 2 * T;
+    const float* gb = xg + (size_t)b * 6 * T;
+    float mean[6], sd[6], x[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        mean[c] = xm[c];
+        sd[c] = xs[c];
+        x[c] = __fadd_rn(__fmul_rn(eb[(size_t)c * e_sc], sd[c]), mean[c]);   // _denorm_x
+    }
+    const bool un = um && us;
+    const float us0 = un ? us[0] : 1.0f, us1 = un ? us[1] : 1.0f, um0 = un ? um[0] : 0.0f, um1 = un ? um[1] : 0.0f;
+    float sxx = 1.0f, syy = 1.0f, S[6][4], g[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) S[r][c] = (r == c + 2) ? 1.0f : 0.0f;
+    double sum = 0.0;
+    // step k's control and target are loaded one step ahead (as knet_rollout_kernel: about one wave per SIMD, so no
+    // other wave hides the load latency of the serial chain)
+    float ud = 0.0f, ue = 0.0f, tg[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (valid > 0) {
+        ud = ub[t];
+        ue = ub[T + t];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) tg[c] = gb[(size_t)c * T + t + 1];
+    }
+    for (int k = 1; k <= valid; ++k) {
+        float cd = ud, ce = ue, ct[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) ct[c] = tg[c];
+        if (k < valid) {
+            ud = ub[t + k];
+            ue = ub[T + t + k];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) tg[c] = gb[(size_t)c * T + t + k + 1];
+        }
+        if (un) {   // _denorm_u
+            cd = __fadd_rn(__fmul_rn(cd, us0), um0);
+            ce = __fadd_rn(__fmul_rn(ce, us1), um1);
+        }
+        float xn[6];
+        VehJac J;
+        veh_step_t<true>(p, L, Ts, x, cd, ce, xn, &J);
+        // S <- d xn / d x . S
+        float Sn[6][4];
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float a = 0.0f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) a = fmaf(J.A[r][q], S[2 + q][c], a);
+                Sn[r][c] = J.post[r] * fmaf(Ts, a, S[r][c]);
+            }
+        sxx *= J.post[0];
+        syy *= J.post[1];
+        // _compute_step_loss_real against x_gt_norm * x_std + x_mean
+        float e[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) e[c] = __fsub_rn(xn[c], __fadd_rn(__fmul_rn(ct[c], sd[c]), mean[c]));
+        e[2] = atan2f(sinf(e[2]), cosf(e[2]));
+        float s = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) s = __fadd_rn(s, __fmul_rn(e[c], e[c]));
+        sum += (double)s;
+        g[0] = fmaf(e[0], sxx, g[0]);
+        g[1] = fmaf(e[1], syy, g[1]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int r = 0; r < 6; ++r) g[2 + c] = fmaf(e[r], Sn[r][c], g[2 + c]);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            x[r] = xn[r];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) S[r][c] = Sn[r][c];
+        }
+    }
+    const float inv = valid > 0 ? 1.0f / (6.0f * (float)valid) : 0.0f;
+    part[i] = valid > 0 ? (float)(sum / (6.0 * (double)valid)) : 0.0f;
+    if (grad) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c)   // d e^2 = 2 e de; the x_std of the denormalization
+            grad[((size_t)b * 6 + c) * nwin + w] = valid > 0 ? __fmul_rn(__fmul_rn(2.0f * g[c], sd[c]), inv) : 0.0f;
     }
 }
 
@@ -1421,6 +1584,25 @@ int traj_knet_rollout_eval_f32(const traj_vehicle_params* p, const traj_knet_lim
     hipLaunchKernelGGL(knet_rollout_kernel, dim3(nblk((long long)B * nwin, 64)), dim3(64), 0, (hipStream_t)stream, k,
                        *lim, Ts, B, T, H, t0, step, nwin, x_est, e_sb, e_sc, e_st, x_mean, x_std, u, x_gt, ade, fde,
                        x_gt ? err_profile : nullptr, pred);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+int traj_knet_pred_loss_f32(const traj_vehicle_params* p, const traj_knet_limits* lim, float Ts, int B, int T, int H,
+                            int t0, int step, int nwin, const float* x_est, int e_sb, int e_sc, int e_sw,
+                            const float* x_mean, const float* x_std, const float* u_mean, const float* u_std,
+                            const float* u, const float* x_gt_norm, float* part, float* grad, void* stream) {
+    if (!p || !lim || B < 0 || T < 1 || H < 1 || t0 < 0 || step < 1 || nwin < 0) return TRAJ_E_ARG;
+    // every window starts inside the sequence (a window at t = T - 1 has no step and scores 0)
+    if (nwin > 0 && (long long)t0 + (long long)(nwin - 1) * step > (long long)T - 1) return TRAJ_E_ARG;
+    if ((long long)B * nwin > 0x7fffffffLL || e_sb < 0 || e_sc < 0 || e_sw < 0) return TRAJ_E_ARG;
+    if (B == 0 || nwin == 0) return TRAJ_OK;
+    if (!x_est || !x_mean || !x_std || !u || !x_gt_norm || !part || (!u_mean) != (!u_std)) return TRAJ_E_ARG;
+    KP k{(float)p->Cm1, (float)p->Cm2, (float)p->Cr0, (float)p->Cr2, (float)p->Br, (float)p->Cr, (float)p->Dr,
+         (float)p->Bf,  (float)p->Cf,  (float)p->Df,  (float)p->m,   (float)p->Iz, (float)p->lf, (float)p->lr,
+         (float)p->maxAlpha, (float)p->vx_zero};
+    hipLaunchKernelGGL(knet_pred_loss_kernel, dim3(nblk((long long)B * nwin, 64)), dim3(64), 0, (hipStream_t)stream,
+                       k, *lim, Ts, B, T, H, t0, step, nwin, x_est, e_sb, e_sc, e_sw, x_mean, x_std, u_mean, u_std, u,
+                       x_gt_norm, part, grad);
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
 }
 

@@ -24,6 +24,9 @@ Training (``knet_train.py``): with autograd on, the three HIP
 ``torch.autograd.Function`` s whose backward re-evaluates the same step in torch ops on the device
 and differentiates it -- the expressions of vehicle_model.py / kalman_net.py that the reference's
 autograd differentiates (clamp, max and atan2 subgradients included); the GEMMs are torch's.
+``VehicleModel.f`` is differentiable the same way.  Training with the open-loop prediction loss (f6,
+``pipeline_prediction.py``): ``knet_pred_loss`` (``traj_knet_pred_loss_f32``) rolls the physics H steps from every
+posterior of a chunk in one launch and returns the losses with their analytic gradient.
 """
 from __future__ import annotations
 
@@ -77,6 +80,31 @@ def knet_prior(params: dict, Ts: float, x_post, u, x_mean, x_std, y_mean, y_std,
         C.byref(params_struct(params)), C.byref(limits_struct(params)), float(Ts), B, _p(xp), _p(uu), _p(yy),
         *[_p(t) for t in norm], _p(prior), _p(m1y), _p(dy), _stream()), "traj_knet_prior_f32")
     return prior, m1y, dy
+
+
+def knet_pred_loss(params: dict, Ts: float, x_est, t0: int, step: int, u, x_gt_norm, H: int, x_mean, x_std,
+                   u_mean=None, u_std=None, want_grad=True):
+    """traj_knet_pred_loss_f32 (include/trajknet.h): x_est [B,6,nwin] normalized posteriors indexed by window (any
+    strides; window w starts at t0 + w * step), u [B,2,T], x_gt_norm [B,6,T] -> (part [B,nwin], grad [B,6,nwin] or
+    None): the H-step open-loop prediction loss of every window and its gradient w.r.t. x_est."""
+    dev = x_est.device
+    B, T = u.shape[0], u.shape[2]
+    if x_est.dim() != 3 or x_est.shape[:2] != (B, 6) or x_gt_norm.shape != (B, 6, T) or u.shape[1] != 2:
+        raise ValueError("knet_pred_loss: x_est [B,6,nwin], u [B,2,T] and x_gt_norm [B,6,T] must match")
+    nwin = x_est.shape[2]
+    xe = x_est.detach()
+    if xe.dtype != torch.float32 or min(xe.stride()) < 0:
+        xe = xe.float().contiguous()
+    uu, xg = u.detach().float().contiguous(), x_gt_norm.detach().float().contiguous()
+    # bound to locals: a temporary's storage would go back to the allocator before the launch
+    norm = [None if t is None else t.detach().reshape(-1).float().contiguous() for t in (x_mean, x_std, u_mean, u_std)]
+    part = torch.empty((B, nwin), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, 6, nwin), dtype=torch.float32, device=dev) if want_grad else None
+    _lib.check(_lib.lib().traj_knet_pred_loss_f32(
+        C.byref(params_struct(params)), C.byref(limits_struct(params)), float(Ts), B, T, int(H), int(t0), int(step),
+        nwin, _p(xe), *[int(s) for s in xe.stride()], *[_p(t) for t in norm], _p(uu), _p(xg), _p(part), _p(grad),
+        _stream()), "traj_knet_pred_loss_f32")
+    return part, grad
 
 
 def _gru_gates(gi, gh, h):
@@ -223,6 +251,14 @@ class VehicleModel:
         dev = x_batch_in.device
         one6 = torch.ones(6, dtype=torch.float32, device=dev)
         one5 = torch.ones(5, dtype=torch.float32, device=dev)
+        if torch.is_grad_enabled() and x_batch_in.requires_grad:
+            # the same kernel under autograd (the reference differentiates f: pipeline_prediction.py:82)
+            B = x_batch_in.shape[0]
+            prior, _, _ = _KnetPriorFn.apply(x_batch_in.float().reshape(B, 6), u_batch_in.float().reshape(B, 2),
+                                             torch.zeros((B, 5), dtype=torch.float32, device=dev), self.Params,
+                                             self.Ts, (torch.zeros_like(one6), one6, torch.zeros_like(one5), one5,
+                                                       None, None))
+            return prior.unsqueeze(2)
         prior, _, _ = knet_prior(self.Params, self.Ts, x_batch_in.float(), u_batch_in.float(),
                                  torch.zeros_like(one6), one6, torch.zeros_like(one5), one5)
         return prior.unsqueeze(2)
@@ -620,5 +656,5 @@ def ekf_run(params: dict, Ts: float, y, u, x0, P0=EKF_P0, Q=EKF_Q, R=EKF_R):
     return out
 
 
-# torch.ops.trajknet.* (prior, gru_gates, update, pack, step): the same HIP ops registered with torch.library
+# torch.ops.trajknet.* (prior, gru_gates, update, pred_loss, pack, step): the same HIP ops registered with torch.library
 from . import knet_ops  # noqa: E402,F401

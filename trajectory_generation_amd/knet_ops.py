@@ -5,14 +5,18 @@
   torch.ops.trajknet.gru_gates(gi, gh, h) -> h_out       one torch.nn.GRU cell's gates (traj_knet_gru_gates_f32)
   torch.ops.trajknet.update(m1x_prior, KG, dy, innov_logit) -> x_post
                                                           kalman_net.py:169-178 (traj_knet_update_f32)
-  torch.ops.trajknet.pack(weights, dims) -> packed        the fused kernels' packed weight copy (traj_knet_pack_f32)
+  torch.ops.trajknet.pred_loss(x_est, u, x_gt_norm, x_mean, x_std, u_mean, u_std, params, limits, Ts, horizon, t0, step)
+      -> (part [B,nwin], grad [B,6,nwin])                 pipeline_prediction.py:45-99 for every window at once
+                                                          (traj_knet_pred_loss_f32; x_est [B,6,nwin] read by stride)
+  torch.ops.trajknet.pack(weights, dims) -> packed       the fused kernels' packed weight copy (traj_knet_pack_f32)
   torch.ops.trajknet.step(y, u, x_post, h_q, h_sigma, h_s, packed, weights, dims, params, limits, Ts, norm)
       -> (x_post, h_q, h_sigma, h_s, KG)                  kalman_net.py:145-216, one whole eval-mode step as the
                                                           fused front -> fc2 -> back launches
 
 Functional: no input is modified (the step's hidden states come back as new tensors).  Every op has a fake
 (meta) kernel, so shapes propagate under FakeTensorMode / torch.compile tracing without a GPU; prior,
-gru_gates and update carry autograd formulas (the reference's expressions, as knet.py's training path).
+gru_gates and update carry autograd formulas (the reference's expressions, as knet.py's training path), pred_loss the
+kernel's own gradient (its second output).
 The real kernels need the HIP library and a GPU -- there is no CPU implementation.
 
 ``weights`` is the list ``step_weights(model)`` returns (traj_knet_net's pointer fields, in order),
@@ -242,6 +246,38 @@ def _update_backward(ctx, g):
 
 
 update.register_autograd(_update_backward, setup_context=_update_setup)
+
+
+# ---------------------------------------------------------------- open-loop prediction loss (training)
+
+@custom_op("trajknet::pred_loss", mutates_args=())
+def pred_loss(x_est: torch.Tensor, u: torch.Tensor, x_gt_norm: torch.Tensor, x_mean: torch.Tensor,
+              x_std: torch.Tensor, u_mean: Optional[torch.Tensor], u_std: Optional[torch.Tensor], params: List[float],
+              limits: List[float], Ts: float, horizon: int, t0: int, step: int) -> tuple[torch.Tensor, torch.Tensor]:
+    from .knet import knet_pred_loss
+    p = dict(zip(PARAM_KEYS, params))
+    p.update(zip(LIMIT_KEYS, limits))
+    with torch.cuda.device(x_est.device):   # the launcher runs on the current stream
+        return knet_pred_loss(p, Ts, x_est, t0, step, u, x_gt_norm, horizon, x_mean, x_std, u_mean, u_std)
+
+
+@register_fake("trajknet::pred_loss")
+def _pred_loss_fake(x_est, u, x_gt_norm, x_mean, x_std, u_mean, u_std, params, limits, Ts, horizon, t0, step):
+    B, nwin = x_est.shape[0], x_est.shape[2]
+    return x_est.new_empty((B, nwin), dtype=torch.float32), x_est.new_empty((B, 6, nwin), dtype=torch.float32)
+
+
+def _pred_loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _pred_loss_backward(ctx, g_part, g_grad):
+    """d part / d x_est is the op's second output (a first derivative only: that output carries no gradient)."""
+    grad, = ctx.saved_tensors
+    return (g_part.unsqueeze(1) * grad,) + (None,) * 12
+
+
+pred_loss.register_autograd(_pred_loss_backward, setup_context=_pred_loss_setup)
 
 
 # ---------------------------------------------------------------- fused step (inference)
