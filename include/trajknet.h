@@ -168,6 +168,46 @@ int traj_knet_pred_loss_f32(const traj_vehicle_params* p, const traj_knet_limits
                             const float* x_mean, const float* x_std, const float* u_mean, const float* u_std,
                             const float* u, const float* x_gt_norm, float* part, float* grad, void* stream);
 
+/* Truncated-BPTT training without autograd (knet_train_fused.py): the non-GEMM parts of one step's backward and the
+ * chunk loss.  All float32, deterministic (no atomics, every sum in a fixed order).  The derivatives are the ones
+ * torch's autograd gives for the forward expressions above: clamp passes the gradient on the closed interval,
+ * abs'(0) = 0, max(|vx|, vx_zero) halves a tie, ReLU passes it where its output is > 0.
+ *
+ * traj_knet_prior_bwd_f32: the transposed chain of traj_knet_prior_f32 from the saved posterior,
+ *   g_x_post [B,6] = d (g_prior . m1x_prior + g_dy . dy) / d x_post   (g_dy may be NULL; u is not differentiated).
+ * traj_knet_gru_gates_bwd_f32: of traj_knet_gru_gates_f32, r / z / n recomputed from gi, gh [B,3H] and h [B,H];
+ *   the incoming gradient is g_out[b*g_out_ld + k] (+ g_out2[b*g_out2_ld + k] when g_out2 != NULL: a slice of a wider
+ *   matrix is read in place); writes g_gi, g_gh [B,3H] and g_h [B,H] (the direct path z * g only; the caller adds
+ *   g_gh W_hh).
+ * traj_knet_update_bwd_f32: of traj_knet_update_f32 with g = g_post (+ g_post2 when not NULL), both [B,6]:
+ *   g_prior = g, g_KG [B,30], g_dy [B,5], g_logit [B] per sequence (the caller sums it over b and t).
+ * traj_knet_dense_bwd_f32: a dense layer's epilogue on the way back,
+ *   g_pre[r, c] = (g_a[r*ld_a + c] + g_b[r*ld_b + c]) * mask[r, c] * (act[r, c] > 0)
+ *   with g_b, mask (the dropout mask, {0, 1/(1-p)}) and act (the saved post-activation) each optional (NULL);
+ *   act, mask, g_pre are [rows, cols]; g_pre may alias g_a when ld_a == cols.
+ * traj_knet_train_loss_f32: pipeline.py:22-60 over a chunk's stacked posteriors x_out[b*sb + c*sc + k*sk]
+ *   (b < B, c < 6, k < K) against x_tgt [B,6,K] (normalized):
+ *     loss_x = 5/6 mean_{c != 2} (x_out - x_tgt)^2 + 1/6 mean wrap(phi_out - phi_tgt)^2   (phi denormalized with
+ *              x_mean / x_std [6]; wrap = atan2(sin, cos), derivative 1)
+ *     loss   = alpha loss_x + (1 - alpha) mean (x_out[c != 2] - y_tgt)^2   (y_tgt [B,5,K]; alpha = 1: y_tgt unused)
+ *   accumulated in float64 in a fixed order, written as one float32 to loss[0]; grad (same strides as x_out)
+ *   receives d loss / d x_out + g_extra [B,6,K] (contiguous; NULL: none). */
+int traj_knet_prior_bwd_f32(const traj_vehicle_params* p, const traj_knet_limits* lim, float Ts, int B,
+                            const float* x_post, const float* u, const float* x_mean, const float* x_std,
+                            const float* y_mean, const float* y_std, const float* u_mean, const float* u_std,
+                            const float* g_prior, const float* g_dy, float* g_x_post, void* stream);
+int traj_knet_gru_gates_bwd_f32(int B, int H, const float* gi, const float* gh, const float* h, const float* g_out,
+                                int g_out_ld, const float* g_out2, int g_out2_ld, float* g_gi, float* g_gh, float* g_h,
+                                void* stream);
+int traj_knet_update_bwd_f32(int B, const float* KG, const float* dy, const float* innov_logit, const float* g_post,
+                             const float* g_post2, float* g_prior, float* g_KG, float* g_dy, float* g_logit,
+                             void* stream);
+int traj_knet_dense_bwd_f32(int rows, int cols, const float* g_a, int ld_a, const float* g_b, int ld_b,
+                            const float* act, const float* mask, float* g_pre, void* stream);
+int traj_knet_train_loss_f32(int B, int K, const float* x_out, int sb, int sc, int sk, const float* x_tgt,
+                             const float* y_tgt, const float* x_mean, const float* x_std, float alpha,
+                             const float* g_extra, float* loss, float* grad, void* stream);
+
 /* Build-defined EKF baseline for config 5 ("MSE vs reference EKF"; the reference has no EKF, SURVEY.md
  * 8(f) f2), float64, one thread per sequence, all T steps in one launch:
  *   predict  x- = f(x+, u_t) (the clamped vehicle_model.py:109-134 step), F = df/dx by central

@@ -181,6 +181,13 @@ _SIGS = {
     "traj_knet_pred_loss_f32": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_float, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _V, C.c_int, C.c_int, C.c_int,
                                           _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_knet_prior_bwd_f32": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_float, C.c_int,
+                                          _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_knet_gru_gates_bwd_f32": (C.c_int, [C.c_int, C.c_int, _V, _V, _V, _V, C.c_int, _V, C.c_int, _V, _V, _V, _V]),
+    "traj_knet_update_bwd_f32": (C.c_int, [C.c_int, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_knet_dense_bwd_f32": (C.c_int, [C.c_int, C.c_int, _V, C.c_int, _V, C.c_int, _V, _V, _V, _V]),
+    "traj_knet_train_loss_f32": (C.c_int, [C.c_int, C.c_int, _V, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V, C.c_float,
+                                           _V, _V, _V, _V]),
     "traj_ekf_run_f64": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_double, C.c_int, C.c_int,
                                    _V, _V, _V, _V, _V, _V, _V, _V]),
     "traj_gen_abi_version": (C.c_int, []),

@@ -355,6 +355,9 @@ __global__ __launch_bounds__(64) void knet_pred_loss_kernel(KP p, traj_knet_limi
     }
 }
 
+// the backward kernels and the chunk loss of truncated-BPTT training (traj_knet_*_bwd_f32, traj_knet_train_loss_f32)
+#include "knet_bwd.h"
+
 // ---------------------------------------------------------------- fused step (throughput path)
 // One KalmanNet step in two kernels around FC2 (kalman_net.py:145-216, eval mode):
 //   front: prior -> FC5 -> GRU_Q -> GRU_Sigma -> FC1, FC7 -> GRU_S, writing x2 = [out_Sigma | h_S]
@@ -1603,6 +1606,68 @@ int traj_knet_pred_loss_f32(const traj_vehicle_params* p, const traj_knet_limits
     hipLaunchKernelGGL(knet_pred_loss_kernel, dim3(nblk((long long)B * nwin, 64)), dim3(64), 0, (hipStream_t)stream,
                        k, *lim, Ts, B, T, H, t0, step, nwin, x_est, e_sb, e_sc, e_sw, x_mean, x_std, u_mean, u_std, u,
                        x_gt_norm, part, grad);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+int traj_knet_prior_bwd_f32(const traj_vehicle_params* p, const traj_knet_limits* lim, float Ts, int B,
+                            const float* x_post, const float* u, const float* x_mean, const float* x_std,
+                            const float* y_mean, const float* y_std, const float* u_mean, const float* u_std,
+                            const float* g_prior, const float* g_dy, float* g_x_post, void* stream) {
+    if (!p || !lim || B < 0) return TRAJ_E_ARG;
+    if (B == 0) return TRAJ_OK;
+    if (!x_post || !u || !x_mean || !x_std || !y_mean || !y_std || !g_prior || !g_x_post) return TRAJ_E_ARG;
+    if ((!u_mean) != (!u_std)) return TRAJ_E_ARG;
+    KP k{(float)p->Cm1, (float)p->Cm2, (float)p->Cr0, (float)p->Cr2, (float)p->Br, (float)p->Cr, (float)p->Dr,
+         (float)p->Bf,  (float)p->Cf,  (float)p->Df,  (float)p->m,   (float)p->Iz, (float)p->lf, (float)p->lr,
+         (float)p->maxAlpha, (float)p->vx_zero};
+    hipLaunchKernelGGL(knet_prior_bwd_kernel, dim3(nblk(B, 256)), dim3(256), 0, (hipStream_t)stream, k, *lim, Ts, B,
+                       x_post, u, x_mean, x_std, y_std, u_mean, u_std, g_prior, g_dy, g_x_post);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+int traj_knet_gru_gates_bwd_f32(int B, int H, const float* gi, const float* gh, const float* h, const float* g_out,
+                                int g_out_ld, const float* g_out2, int g_out2_ld, float* g_gi, float* g_gh, float* g_h,
+                                void* stream) {
+    if (B < 0 || H < 1 || (long long)B * H > 0x7fffffffLL / 3) return TRAJ_E_ARG;
+    if (B == 0) return TRAJ_OK;
+    if (!gi || !gh || !h || !g_out || !g_gi || !g_gh || !g_h) return TRAJ_E_ARG;
+    if (g_out_ld < H || (g_out2 && g_out2_ld < H)) return TRAJ_E_ARG;
+    hipLaunchKernelGGL(knet_gru_bwd_kernel, dim3(nblk((long long)B * H, 256)), dim3(256), 0, (hipStream_t)stream, B, H,
+                       gi, gh, h, g_out, g_out_ld, g_out2, g_out2_ld, g_gi, g_gh, g_h);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+int traj_knet_update_bwd_f32(int B, const float* KG, const float* dy, const float* innov_logit, const float* g_post,
+                             const float* g_post2, float* g_prior, float* g_KG, float* g_dy, float* g_logit,
+                             void* stream) {
+    if (B < 0) return TRAJ_E_ARG;
+    if (B == 0) return TRAJ_OK;
+    if (!KG || !dy || !innov_logit || !g_post || !g_prior || !g_KG || !g_dy || !g_logit) return TRAJ_E_ARG;
+    hipLaunchKernelGGL(knet_update_bwd_kernel, dim3(nblk(B, 256)), dim3(256), 0, (hipStream_t)stream, B, KG, dy,
+                       innov_logit, g_post, g_post2, g_prior, g_KG, g_dy, g_logit);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+int traj_knet_dense_bwd_f32(int rows, int cols, const float* g_a, int ld_a, const float* g_b, int ld_b,
+                            const float* act, const float* mask, float* g_pre, void* stream) {
+    if (rows < 0 || cols < 1) return TRAJ_E_ARG;
+    if (rows == 0) return TRAJ_OK;
+    if (!g_a || !g_pre || ld_a < cols || (g_b && ld_b < cols)) return TRAJ_E_ARG;
+    const long long n = (long long)rows * cols;
+    if (nblk(n, 256) <= 0 || n > 0x7fffffffLL * 256) return TRAJ_E_ARG;
+    hipLaunchKernelGGL(knet_dense_bwd_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, n, cols, g_a,
+                       ld_a, g_b, ld_b, act, mask, g_pre);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+int traj_knet_train_loss_f32(int B, int K, const float* x_out, int sb, int sc, int sk, const float* x_tgt,
+                             const float* y_tgt, const float* x_mean, const float* x_std, float alpha,
+                             const float* g_extra, float* loss, float* grad, void* stream) {
+    if (B < 1 || K < 1 || sb < 0 || sc < 0 || sk < 0 || !(alpha >= 0.0f && alpha <= 1.0f)) return TRAJ_E_ARG;
+    if ((long long)B * K > 0x7fffffffLL / 6) return TRAJ_E_ARG;
+    if (!x_out || !x_tgt || !x_mean || !x_std || !loss || !grad || (alpha < 1.0f && !y_tgt)) return TRAJ_E_ARG;
+    hipLaunchKernelGGL(knet_train_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, K, x_out, sb, sc, sk,
+                       x_tgt, y_tgt, x_mean, x_std, alpha, g_extra, loss, grad);
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
 }
 

@@ -7,6 +7,9 @@ device (``knet.torch_prior``, ``knet.torch_gru_gates``); clipping and the optimi
 Truncated BPTT as the reference runs it: a loss and a backward every ``K_TBPTT`` steps, then either an
 optimizer step per chunk (``'standard'``) or one per trajectory (``'accumulation'``), and the hidden
 states / posterior detached at every chunk end.
+
+``train_epoch`` with ``params["fused"] = True`` runs the same pass on the autograd-free path of ``knet_train_fused.py``
+(the whole chunk replayed as one HIP graph); the default is the path in this file.
 """
 from __future__ import annotations
 
@@ -106,5 +109,9 @@ def train_epoch(model, optimizer, y_train, u_train, x_train, norm_stats, params)
     x_norm = (x_b - x_mean) / x_std
     x0 = x_norm[:, :, 0]
     m1x0 = (x0 + torch.randn_like(x0) * 0.2).unsqueeze(2)
-    avg, loss_db, _ = tbptt_sequence(model, optimizer, y_norm, u_b, x_norm, m1x0, params, x_mean, x_std)
+    if params.get("fused", False):   # opt-in: the autograd-free chunk replayed as a HIP graph
+        from .knet_train_fused import tbptt_sequence_fused
+        avg, loss_db, _ = tbptt_sequence_fused(model, optimizer, y_norm, u_b, x_norm, m1x0, params, x_mean, x_std)
+    else:
+        avg, loss_db, _ = tbptt_sequence(model, optimizer, y_norm, u_b, x_norm, m1x0, params, x_mean, x_std)
     return avg, loss_db

@@ -159,6 +159,72 @@ def tbptt_prediction_sequence(model, optimizer, y_norm, u, x_norm, m1x0, params,
     return lf, lp
 
 
+class _PredExtra:
+    """The prediction loss inside a fused chunk (knet_train_fused.FusedTBPTT.run_chunk's ``extra`` hook): one
+    knet_pred_loss launch on the tape's posteriors, its gradient x lambda_pred / (B Kc) -- the mean over sequences and
+    windows -- written to the loss kernel's g_extra.  The launch's t0 and T are fixed in the captured graph, so it
+    reads a window [c0, c0 + Tw) of u / x_norm copied into static buffers (t0 = 0, T = Tw = min(Kc + H, T - c0))."""
+
+    def __init__(self, model, B, Kc, Tw, H, lambda_pred):
+        self.model, self.Kc, self.Tw, self.H, self.lam = model, Kc, Tw, H, lambda_pred
+        dev = model.device
+        self.u = torch.zeros((B, 2, Tw), dtype=torch.float32, device=dev)
+        self.x = torch.zeros((B, 6, Tw), dtype=torch.float32, device=dev)
+        self.part = None
+
+    def load(self, u, x_norm, c0):
+        self.u.copy_(u[:, :, c0:c0 + self.Tw])
+        self.x.copy_(x_norm[:, :, c0:c0 + self.Tw])
+
+    def __call__(self, runner, Kc):
+        md = self.model
+        xm, xs = md._norm_tensors()[:2]
+        self.part, grad = knet_pred_loss(md.sys.Params, md.sys.Ts, runner.posteriors(Kc), 0, 1, self.u, self.x, self.H,
+                                         xm, xs, md.u_mean, md.u_std)
+        torch.mul(grad, self.lam / (grad.shape[0] * Kc), out=runner.g_extra(Kc))
+
+
+def tbptt_prediction_sequence_fused(model, optimizer, y_norm, u, x_norm, m1x0, params, x_mean, x_std, on_chunk=None):
+    """tbptt_prediction_sequence on the fused path (knet_train_fused.FusedTBPTT): the chunk -- filter steps, prediction
+    loss, state loss, backward sweep, weight-gradient products -- replayed as one HIP graph; clipping and the optimizer
+    as there.  Returns (filter losses, prediction losses) per chunk."""
+    from .knet_train_fused import _publish_state, runner_for
+    K, T = params["K_TBPTT"], params["T"]
+    lambda_pred, H = params.get("lambda_pred", 0.0), params.get("pred_horizon", 0)
+    use_pred = lambda_pred > 0 and H > 0
+    B = y_norm.shape[0]
+    model.batch_size = B
+    model.T = T
+    R = runner_for(model, B, min(K, T))
+    hooks = R.__dict__.setdefault("_pred_hooks", {})
+    R.reset(m1x0)
+    optimizer.zero_grad()
+    lf, lp, Kc = [], [], 0
+    for c0 in range(0, T, K):
+        c1 = min(c0 + K, T)
+        Kc = c1 - c0
+        hook, key = None, None
+        if use_pred:
+            key = (Kc, min(Kc + H, T - c0), H, float(lambda_pred))
+            if key not in hooks:
+                hooks[key] = _PredExtra(model, B, *key)
+            hook = hooks[key]
+            hook.load(u, x_norm, c0)
+        loss = R.run_chunk(y_norm[:, :, c0:c1], u[:, :, c0:c1], x_norm[:, :, c0:c1], composite=False, extra=hook,
+                           extra_key=key)
+        R.add_grads()
+        if on_chunk is not None:
+            on_chunk(model)
+        clip_grad_norm_(model.parameters(), max_norm=CLIP_NORM)
+        optimizer.step()
+        optimizer.zero_grad()
+        lf.append(float(loss.item()))
+        lp.append(float(_batch_mean(hook.part).mean().item()) if use_pred else 0.0)
+        R.carry_over(Kc)
+    _publish_state(model, R, Kc)
+    return lf, lp
+
+
 def _noisy_start(x_norm):
     x0 = x_norm[:, :, 0]
     return (x0 + INIT_NOISE_STD * torch.randn_like(x0)).unsqueeze(2)
@@ -167,7 +233,7 @@ def _noisy_start(x_norm):
 def train_epoch(model, optimizer, y_train, u_train, x_train, norm_stats, params):
     """One TBPTT pass (train mode) over a random batch of N_batch of the N_E trajectories (y / u / x [N_E, c, T] in
     real units) from a noisy normalized first state.  params: N_E, N_batch, K_TBPTT, T, m, device, lambda_pred,
-    pred_horizon (and stepwise=True for the per-step loss path).
+    pred_horizon (and stepwise=True for the per-step loss path, fused=True for the graph path of knet_train_fused.py).
     Returns (average filter loss, average prediction loss, filter loss in dB)."""
     device = params["device"]
     x_mean, x_std = norm_stats["x_mean"].to(device), norm_stats["x_std"].to(device)
@@ -176,8 +242,12 @@ def train_epoch(model, optimizer, y_train, u_train, x_train, norm_stats, params)
     y_b, u_b, x_b = (t[pick].to(device) for t in (y_train, u_train, x_train))
     y_norm = (y_b - norm_stats["y_mean"].to(device)) / norm_stats["y_std"].to(device)
     x_norm = (x_b - x_mean) / x_std
-    lf, lp = tbptt_prediction_sequence(model, optimizer, y_norm, u_b, x_norm, _noisy_start(x_norm), params, x_mean,
-                                       x_std, stepwise=params.get("stepwise", False))
+    if params.get("fused", False):   # opt-in: the autograd-free chunk replayed as a HIP graph
+        lf, lp = tbptt_prediction_sequence_fused(model, optimizer, y_norm, u_b, x_norm, _noisy_start(x_norm), params,
+                                                 x_mean, x_std)
+    else:
+        lf, lp = tbptt_prediction_sequence(model, optimizer, y_norm, u_b, x_norm, _noisy_start(x_norm), params, x_mean,
+                                           x_std, stepwise=params.get("stepwise", False))
     avg_filter = sum(lf) / max(1, len(lf))
     avg_pred = sum(lp) / max(1, len(lp)) if params.get("lambda_pred", 0.0) > 0 else 0.0
     return avg_filter, avg_pred, 10 * torch.log10(torch.tensor(avg_filter).clamp_min(EPS_DB))
@@ -232,8 +302,9 @@ class Pipeline_Vehicle_KNet:
         self.norm_stats, self.device = norm_stats, device
         self.N_E, self.N_CV, self.N_T = len(self.y_train), len(self.y_val), len(self.y_test)
 
-    def set_training_params(self, n_steps, n_batch, lr, wd, K_TBPTT, T, lambda_pred=0.0, pred_horizon=0):
-        self.N_steps, self.N_batch, self.lr, self.wd = n_steps, n_batch, lr, wd
+    def set_training_params(self, n_steps, n_batch, lr, wd, K_TBPTT, T, lambda_pred=0.0, pred_horizon=0, fused=False):
+        """fused=True: train on the autograd-free graph path (knet_train_fused.py)."""
+        self.N_steps, self.N_batch, self.lr, self.wd, self.fused = n_steps, n_batch, lr, wd, fused
         self.K_TBPTT, self.T = K_TBPTT, T
         self.m, self.n = self.sys_model.m, self.sys_model.n
         self.lambda_pred, self.pred_horizon = lambda_pred, pred_horizon
@@ -254,7 +325,7 @@ class Pipeline_Vehicle_KNet:
         best = float("inf")
         val_set = self._normalized(self.y_val, self.u_val, self.x_val)
         train_params = dict(self._eval_params(self.N_CV), N_E=self.N_E, N_batch=self.N_batch, K_TBPTT=self.K_TBPTT,
-                            lambda_pred=self.lambda_pred, pred_horizon=self.pred_horizon)
+                            lambda_pred=self.lambda_pred, pred_horizon=self.pred_horizon, fused=self.fused)
         for epoch in range(self.N_steps):
             avg_filt, avg_pred, train_db = train_epoch(self.model, self.optimizer, self.y_train, self.u_train,
                                                        self.x_train, self.norm_stats, train_params)
