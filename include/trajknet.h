@@ -16,6 +16,8 @@
  *     open-loop rollout + ADE / FDE
  *   pipeline_prediction.py:45-99 prediction loss of         traj_knet_pred_loss_f32 (+ its gradient w.r.t. the
  *     training (H-step rollout from every posterior)          posteriors)
+ *   pipeline_indipendent_chunking.py:89-144 batch of        traj_knet_chunk_gather_f32, traj_knet_clip_adamw_f32
+ *     shuffled chunks, clipping, AdamW                        (around the fused chunk of knet_train_fused.py)
  *   (no reference counterpart) EKF baseline of config 5     traj_ekf_run_f64
  *
  * Conventions as trajmpc.h: device pointers, row-major, asynchronous on `stream`, 0 / TRAJ_E_*.
@@ -207,6 +209,49 @@ int traj_knet_dense_bwd_f32(int rows, int cols, const float* g_a, int ld_a, cons
 int traj_knet_train_loss_f32(int B, int K, const float* x_out, int sb, int sc, int sk, const float* x_tgt,
                              const float* y_tgt, const float* x_mean, const float* x_std, float alpha,
                              const float* g_extra, float* loss, float* grad, void* stream);
+
+/* Chunk-and-shuffle training (pipeline_indipendent_chunking.py) with the whole optimizer update inside the captured
+ * graph: the batch gather in front of the fused chunk and clipping + AdamW behind it.  Both are plain launch
+ * sequences (no allocation, copy or synchronisation), deterministic (no atomics, every sum in a fixed order).
+ *
+ * traj_knet_chunk_gather_f32: one batch of B chunks of Tc steps out of the full trajectories y [n_traj,5,T_full],
+ *   u [n_traj,2,T_full], x [n_traj,6,T_full] (real units), in one launch.  chunk_ids [B] (int32, device): id c is
+ *   trajectory c / cpt, steps [(c % cpt) Tc, + Tc) with cpt = T_full / Tc (the tail T_full % Tc is never read, as
+ *   training_indipendent_chunking.py:14-34 create_chunks).  Written in the fused chunk's layouts:
+ *     Y [Tc,B,5]     = (y - y_mean) / y_std          U [Tc,B,2] = u
+ *     x_tgt [B,6,Tc] = (x - x_mean) / x_std          y_tgt [B,5,Tc] = Y's values (NULL: not written)
+ *     m1x0 [B,6]     = x_tgt[:, :, 0] + noise_std * noise   (noise [B,6]; NULL: no noise)
+ *   one IEEE subtraction and one IEEE division per value: the bits of the same float32 torch expression.  A row whose
+ *   id is outside [0, n_traj cpt) reads nothing and is written as zeros.  TRAJ_E_ARG for B < 1, n_traj < 1, Tc < 1,
+ *   Tc > T_full, B Tc or n_traj T_full too large for 32-bit indexing, or a missing pointer.
+ *
+ * traj_knet_clip_adamw_f32: torch.nn.utils.clip_grad_norm_ followed by one torch.optim.AdamW step (amsgrad and
+ *   maximize off) over a device-resident table of n_tensors entries, as two launches (norm pass, update pass):
+ *     total = sqrt(sum g^2) over every entry (accumulated in float64 in a fixed order), written to total_norm[0]
+ *             (NULL: not written) as clip_grad_norm_ returns it;
+ *     coef  = min(1, max_norm / (total + 1e-6));  max_norm <= 0: no clipping;      g' = coef g  (g is only read)
+ *     t     = ++step[0]  (device int32: the norm pass stores it from one thread, the update pass reads it)
+ *     p <- p (1 - lr wd);  m <- m + (1 - beta1)(g' - m);  v <- beta2 v + (1 - beta2) g'^2;
+ *     p <- p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   lr is read from the device scalar lr[0], so a scheduler changes it without a new capture.  Entry pointers need
+ *   only float alignment and n >= 1; n_total, the sum of the entries' n, sizes the grids only.  ws: at least
+ *   traj_knet_clip_adamw_workspace_bytes() bytes, 8-byte aligned.  TRAJ_E_ARG for n_tensors < 1, n_total < n_tensors,
+ *   betas outside [0, 1), a missing pointer or a workspace that is too small. */
+typedef struct {
+    float* p;        /* parameter */
+    const float* g;  /* its gradient */
+    float* m;        /* exp_avg */
+    float* v;        /* exp_avg_sq */
+    long long n;     /* elements */
+} traj_knet_opt_entry;
+int traj_knet_chunk_gather_f32(int n_traj, int T_full, int Tc, int B, const float* y, const float* u, const float* x,
+                               const int* chunk_ids, const float* x_mean, const float* x_std, const float* y_mean,
+                               const float* y_std, const float* noise, float noise_std, float* Y, float* U,
+                               float* x_tgt, float* y_tgt, float* m1x0, void* stream);
+size_t traj_knet_clip_adamw_workspace_bytes(void);
+int traj_knet_clip_adamw_f32(const traj_knet_opt_entry* table, int n_tensors, long long n_total, const float* lr,
+                             double beta1, double beta2, double eps, double weight_decay, double max_norm, int* step,
+                             float* total_norm, void* ws, size_t ws_bytes, void* stream);
 
 /* Build-defined EKF baseline for config 5 ("MSE vs reference EKF"; the reference has no EKF, SURVEY.md
  * 8(f) f2), float64, one thread per sequence, all T steps in one launch:

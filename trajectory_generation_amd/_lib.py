@@ -83,6 +83,11 @@ class KnetNet(C.Structure):
         ("d_fc2h", C.c_int)] + [(k, C.c_void_p) for k in ("fc2a_w", "fc2a_b", "fc2b_w", "fc2b_b")]
 
 
+class KnetOptEntry(C.Structure):
+    """traj_knet_opt_entry (one tensor of traj_knet_clip_adamw_f32's device-resident table)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_longlong)]
+
+
 class GenConfig(C.Structure):
     """traj_gen_config (include/trajgen.h: limits of generation_type1.py:251, :287-288, state clip of :81-82)."""
     _fields_ = [
@@ -188,6 +193,11 @@ _SIGS = {
     "traj_knet_dense_bwd_f32": (C.c_int, [C.c_int, C.c_int, _V, C.c_int, _V, C.c_int, _V, _V, _V, _V]),
     "traj_knet_train_loss_f32": (C.c_int, [C.c_int, C.c_int, _V, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V, C.c_float,
                                            _V, _V, _V, _V]),
+    "traj_knet_chunk_gather_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V, _V, _V, _V, _V, _V,
+                                             C.c_float, _V, _V, _V, _V, _V, _V]),
+    "traj_knet_clip_adamw_workspace_bytes": (C.c_size_t, []),
+    "traj_knet_clip_adamw_f32": (C.c_int, [_V, C.c_int, C.c_longlong, _V, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, _V, _V, _V, C.c_size_t, _V]),
     "traj_ekf_run_f64": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_double, C.c_int, C.c_int,
                                    _V, _V, _V, _V, _V, _V, _V, _V]),
     "traj_gen_abi_version": (C.c_int, []),

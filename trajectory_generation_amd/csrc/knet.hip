@@ -357,6 +357,9 @@ __global__ __launch_bounds__(64) void knet_pred_loss_kernel(KP p, traj_knet_limi
 
 // the backward kernels and the chunk loss of truncated-BPTT training (traj_knet_*_bwd_f32, traj_knet_train_loss_f32)
 #include "knet_bwd.h"
+// the batch gather and clipping + AdamW of chunk-and-shuffle training (traj_knet_chunk_gather_f32,
+// traj_knet_clip_adamw_f32)
+#include "knet_opt.h"
 
 // ---------------------------------------------------------------- fused step (throughput path)
 // One KalmanNet step in two kernels around FC2 (kalman_net.py:145-216, eval mode):
@@ -1668,6 +1671,46 @@ int traj_knet_train_loss_f32(int B, int K, const float* x_out, int sb, int sc, i
     if (!x_out || !x_tgt || !x_mean || !x_std || !loss || !grad || (alpha < 1.0f && !y_tgt)) return TRAJ_E_ARG;
     hipLaunchKernelGGL(knet_train_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, K, x_out, sb, sc, sk,
                        x_tgt, y_tgt, x_mean, x_std, alpha, g_extra, loss, grad);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+int traj_knet_chunk_gather_f32(int n_traj, int T_full, int Tc, int B, const float* y, const float* u, const float* x,
+                               const int* chunk_ids, const float* x_mean, const float* x_std, const float* y_mean,
+                               const float* y_std, const float* noise, float noise_std, float* Y, float* U,
+                               float* x_tgt, float* y_tgt, float* m1x0, void* stream) {
+    if (B < 1 || n_traj < 1 || Tc < 1 || Tc > T_full) return TRAJ_E_ARG;
+    if ((long long)B * Tc > 0x7fffffffLL / 6 || (long long)n_traj * T_full > 0x7fffffffLL / 6) return TRAJ_E_ARG;
+    if (!y || !u || !x || !chunk_ids || !x_mean || !x_std || !y_mean || !y_std || !Y || !U || !x_tgt || !m1x0)
+        return TRAJ_E_ARG;
+    hipLaunchKernelGGL(knet_chunk_gather_kernel, dim3(nblk((long long)B * Tc, 256)), dim3(256), 0, (hipStream_t)stream,
+                       n_traj, T_full, Tc, B, y, u, x, chunk_ids, x_mean, x_std, y_mean, y_std, noise, noise_std, Y, U,
+                       x_tgt, y_tgt, m1x0);
+    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+size_t traj_knet_clip_adamw_workspace_bytes(void) { return (size_t)OPT_NORM_BLOCKS * sizeof(double); }
+
+int traj_knet_clip_adamw_f32(const traj_knet_opt_entry* table, int n_tensors, long long n_total, const float* lr,
+                             double beta1, double beta2, double eps, double weight_decay, double max_norm, int* step,
+                             float* total_norm, void* ws, size_t ws_bytes, void* stream) {
+    if (n_tensors < 1 || n_total < n_tensors) return TRAJ_E_ARG;
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0) ||
+        max_norm != max_norm)
+        return TRAJ_E_ARG;
+    if (!table || !lr || !step || !ws || ((size_t)ws & 7u) || ws_bytes < traj_knet_clip_adamw_workspace_bytes())
+        return TRAJ_E_ARG;
+    // a float4 per thread and sweep: the norm pass in at most OPT_NORM_BLOCKS workgroups (one partial each), the update
+    // pass in at most OPT_MAX_BLOCKS, both grid-striding over the rest
+    const long long want = (n_total + 1023) / 1024;
+    const int nb_norm = (int)(want < OPT_NORM_BLOCKS ? want : OPT_NORM_BLOCKS);
+    const int nb_upd = (int)(want < OPT_MAX_BLOCKS ? want : OPT_MAX_BLOCKS);
+    double* partial = static_cast<double*>(ws);
+    hipLaunchKernelGGL(knet_opt_norm_kernel, dim3(nb_norm), dim3(256), 0, (hipStream_t)stream, table, n_tensors, step,
+                       partial);
+    if (hipGetLastError() != hipSuccess) return TRAJ_E_LAUNCH;
+    hipLaunchKernelGGL(knet_opt_update_kernel, dim3(nb_upd), dim3(256), 0, (hipStream_t)stream, table, n_tensors, lr,
+                       beta1, beta2, eps, weight_decay, max_norm, (const int*)step, (const double*)partial, nb_norm,
+                       total_norm);
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
 }
 

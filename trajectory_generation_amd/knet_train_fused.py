@@ -15,7 +15,9 @@ one weight-gradient product per layer -- so it is captured once and replayed for
   every step writes its pre-activation gradients into the tape;
 * after the sweep each weight gradient is one product over the K B rows of the tape, each bias gradient one column sum,
   into static buffers; ``add_grads`` adds them into the parameters' ``.grad``.  Clipping and the optimizer stay torch's,
-  outside the graph.
+  outside the graph, unless the caller passes them as the ``post`` hook of ``run_chunk`` (``pre`` / ``post``: launches
+  enqueued in front of the first forward step and behind the weight gradients, captured with the chunk -- how
+  pipeline_indipendent_chunking.py makes one optimizer update one replay).
 
 tests/_knet_bptt_ref.py is the same sweep in float64 on the CPU.
 
@@ -120,6 +122,67 @@ def train_loss(x_out, x_tgt, x_mean, x_std, y_tgt=None, alpha=1.0, g_extra=None)
                                             _p(xs), float(alpha), _p(gx), _p(loss), _p(grad), _stream()),
         "traj_knet_train_loss_f32")
     return loss, grad
+
+
+def chunk_gather(y, u, x, chunk_ids, Tc, x_mean, x_std, y_mean, y_std, noise=None, noise_std=0.0, out=None,
+                 want_y_tgt=True):
+    """traj_knet_chunk_gather_f32: the batch of chunks chunk_ids [B] (int32) of Tc steps out of the full trajectories
+    y [n,5,T], u [n,2,T], x [n,6,T] (float32, contiguous, real units) -> (Y [Tc,B,5], U [Tc,B,2], x_tgt [B,6,Tc],
+    y_tgt [B,5,Tc] or None, m1x0 [B,6]).  ``out``: the five destination buffers (y_tgt may be None) instead of new
+    ones -- no allocation then, the form a captured graph takes."""
+    n, _, T = y.shape
+    B = chunk_ids.shape[0]
+    for t, c in ((y, 5), (u, 2), (x, 6)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, c, T):
+            raise ValueError("chunk_gather: y [n,5,T], u [n,2,T], x [n,6,T], contiguous float32")
+    if chunk_ids.dtype != torch.int32 or not chunk_ids.is_contiguous():
+        raise ValueError("chunk_gather: chunk_ids is a contiguous int32 vector")
+    if out is None:
+        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=y.device)   # noqa: E731
+        out = (e(Tc, B, 5), e(Tc, B, 2), e(B, 6, Tc), e(B, 5, Tc) if want_y_tgt else None, e(B, 6))
+    stats = [t.reshape(-1) for t in (x_mean, x_std, y_mean, y_std)]
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in stats):
+        raise ValueError("chunk_gather: contiguous float32 statistics")
+    _ck(_lib.lib().traj_knet_chunk_gather_f32(n, T, int(Tc), B, _p(y), _p(u), _p(x), _p(chunk_ids),
+                                              *[_p(t) for t in stats], _p(noise), float(noise_std),
+                                              *[_p(o) for o in out], _stream()), "traj_knet_chunk_gather_f32")
+    return out
+
+
+class ClipAdamW:
+    """traj_knet_clip_adamw_f32 over the tensors p / g / m / v (lists of equal length; element i of each has the same
+    number of elements; float32, contiguous, on one device; any 4-byte alignment): clip_grad_norm_(max_norm) followed
+    by one AdamW step, two launches per ``step()``, nothing allocated there.  ``lr`` and ``t`` are one-element device
+    tensors (float32 / int32) read by the kernels -- pass existing ones to share them between instances; ``t`` is
+    advanced by every step, ``total_norm`` receives the gradient norm before clipping."""
+
+    def __init__(self, p, g, m, v, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=0.0, t=0):
+        if not (len(p) == len(g) == len(m) == len(v)) or not p:
+            raise ValueError("ClipAdamW: four lists of equal, positive length")
+        dev = p[0].device
+        tab = (_lib.KnetOptEntry * len(p))()
+        for i, quad in enumerate(zip(p, g, m, v)):
+            for a in quad:
+                if a.dtype != torch.float32 or not a.is_contiguous() or a.device != dev or a.numel() < 1 \
+                        or a.numel() != quad[0].numel():
+                    raise ValueError("ClipAdamW: contiguous float32 tensors of one size per entry on one device")
+            tab[i].p, tab[i].g, tab[i].m, tab[i].v = (a.data_ptr() for a in quad)
+            tab[i].n = quad[0].numel()
+        self.n_tensors, self.n_total = len(p), sum(a.numel() for a in p)
+        self.table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self.lr = lr if torch.is_tensor(lr) else torch.tensor([float(lr)], dtype=torch.float32, device=dev)
+        self.t = t if torch.is_tensor(t) else torch.tensor([int(t)], dtype=torch.int32, device=dev)
+        if self.lr.dtype != torch.float32 or self.t.dtype != torch.int32:
+            raise ValueError("ClipAdamW: lr float32, t int32")
+        self.total_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.ws = torch.zeros(_lib.lib().traj_knet_clip_adamw_workspace_bytes() // 8, dtype=torch.float64, device=dev)
+        self.hyper = (float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(max_norm))
+        self._keep = (p, g, m, v)
+
+    def step(self):
+        _ck(_lib.lib().traj_knet_clip_adamw_f32(_p(self.table), self.n_tensors, self.n_total, _p(self.lr), *self.hyper,
+                                                _p(self.t), _p(self.total_norm), _p(self.ws), self.ws.numel() * 8,
+                                                _stream()), "traj_knet_clip_adamw_f32")
 
 
 class FusedTBPTT:
@@ -374,8 +437,10 @@ class FusedTBPTT:
             torch.sum(Dh, 0, out=G[name + ".bias_hh_l0"])
         torch.sum(T["glogit"][:Kc].reshape(1, n), 1, out=G["innov_logit"].reshape(1))
 
-    def _enqueue(self, Kc, alpha, extra):
+    def _enqueue(self, Kc, alpha, extra, pre=None, post=None):
         B = self.B
+        if pre is not None:
+            pre(self, Kc)
         for t in range(Kc):
             self._forward_step(t)
         gx = None
@@ -391,49 +456,65 @@ class FusedTBPTT:
             # step t reads the set written by step t + 1 and writes the other one: step 0 writes carry[(Kc + 1) % 2]
             self._backward_step(t, t == Kc - 1, self.carry[(Kc - t) % 2], self.carry[(Kc - t + 1) % 2])
         self._weight_grads(Kc)
+        if post is not None:
+            post(self, Kc)
 
     def _param_ptrs(self):
         return tuple(v.data_ptr() for v in self.params.values())
 
     @torch.no_grad()
-    def run_chunk(self, y, u, x_tgt, composite=True, alpha=0.8, extra=None, extra_key=None, use_graph=True):
+    def run_chunk(self, y, u, x_tgt, composite=True, alpha=0.8, extra=None, extra_key=None, use_graph=True, pre=None,
+                  post=None, Kc=None):
         """One chunk from the state set by reset / carry_over: y [B,5,Kc] normalized observations (also the composite
         loss's target), u [B,2,Kc], x_tgt [B,6,Kc] normalized targets.  Leaves the loss in ``self.loss`` (returned, a
         1-element device tensor), the gradients in ``self.grads`` and the tape filled.  ``extra(runner, Kc)``, when
         given, is enqueued between the forward and the loss and writes ``g_extra(Kc)``; ``extra_key`` tells graphs
-        with different hooks apart."""
+        with different hooks apart.
+
+        ``pre(runner, Kc)`` is enqueued before the first forward step and ``post(runner, Kc)`` after the weight
+        gradients; both are part of the graph's key.  With ``pre``, y / u / x_tgt may be None (``Kc`` given instead):
+        the hook fills the tape's inputs (T["Y"], T["U"], xt, yt, T["P"][0] and the hidden slots) on the device.
+        ``post`` is left out of the warm-up runs before a capture and runs once per call (an optimizer step there is
+        applied exactly once)."""
         B, T = self.B, self.T
-        Kc = y.shape[2]
-        if not (1 <= Kc <= self.K) or y.shape != (B, 5, Kc) or u.shape != (B, 2, Kc) or x_tgt.shape != (B, 6, Kc):
-            raise ValueError("run_chunk: y [B,5,Kc], u [B,2,Kc], x_tgt [B,6,Kc] with Kc <= K")
+        if y is None:
+            if pre is None or Kc is None or u is not None or x_tgt is not None:
+                raise ValueError("run_chunk: without y / u / x_tgt, a pre hook and Kc are needed")
+            if not (1 <= Kc <= self.K):
+                raise ValueError("run_chunk: 1 <= Kc <= K")
+        else:
+            Kc = y.shape[2]
+            if not (1 <= Kc <= self.K) or y.shape != (B, 5, Kc) or u.shape != (B, 2, Kc) or x_tgt.shape != (B, 6, Kc):
+                raise ValueError("run_chunk: y [B,5,Kc], u [B,2,Kc], x_tgt [B,6,Kc] with Kc <= K")
         if self.model.training != self.train:
             raise ValueError("run_chunk: the model's train / eval mode changed since the runner was built")
-        T["Y"][:Kc].copy_(y.permute(2, 0, 1))
-        T["U"][:Kc].copy_(u.permute(2, 0, 1))
-        self.xt[:B * 6 * Kc].view(B, 6, Kc).copy_(x_tgt)
-        if composite:
-            self.yt[:B * 5 * Kc].view(B, 5, Kc).copy_(y)
+        if y is not None:
+            T["Y"][:Kc].copy_(y.permute(2, 0, 1))
+            T["U"][:Kc].copy_(u.permute(2, 0, 1))
+            self.xt[:B * 6 * Kc].view(B, 6, Kc).copy_(x_tgt)
+            if composite:
+                self.yt[:B * 5 * Kc].view(B, 5, Kc).copy_(y)
         if self.train and not self._explicit_masks:
             self._draw_masks(Kc)
         a = float(alpha) if composite else None
         if not use_graph:
-            self._enqueue(Kc, a, extra)
+            self._enqueue(Kc, a, extra, pre, post)
             return self.loss
         if self.ptrs != self._param_ptrs():   # the captured weight pointers moved: capture again
             self.graphs, self.ptrs = {}, self._param_ptrs()
-        key = (Kc, a, extra_key)
+        key = (Kc, a, extra_key) if pre is None and post is None else (Kc, a, extra_key, pre, post)
         if key not in self.graphs:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                for _ in range(2):   # warm up the library GEMM paths before capture
-                    self._enqueue(Kc, a, extra)
+                for _ in range(2):   # warm up the library GEMM paths before capture (never post: it may step)
+                    self._enqueue(Kc, a, extra, pre)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._enqueue(Kc, a, extra)
+                self._enqueue(Kc, a, extra, pre, post)
             torch.cuda.synchronize()
             self.graph_instantiate_s = time.perf_counter() - t0
             self.graphs[key] = g
