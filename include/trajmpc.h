@@ -245,6 +245,35 @@ int traj_closed_loop_check(const void* workspace, size_t workspace_bytes, int B,
 int traj_dataset_write_csv(const char* clean_path, const char* noisy_path, int B, int T, double Ts,
                            const double* X, const double* U, const double* noise, const long long* ids,
                            int nthreads);
+/* ---- the same files' text formatted on the device (csrc/dataset_fmt.hip; dataset.write_csv_device) ----
+ * Every pointer below is a DEVICE pointer (except traj_dataset_format_f64_host's), `stream` a hipStream_t; the calls
+ * are asynchronous apart from traj_dataset_csv_device_check.  `which` is 0 for the clean file and 1 for the noisy one
+ * (x + noise, one IEEE add, phi dropped); X, U, noise, ids, B, T, Ts as for traj_dataset_write_csv.  The file body is
+ * B * (T + 1) rows in (trajectory, step) order; a call handles rows row0 .. row0 + nrows - 1 (nrows <= INT_MAX), one
+ * row per thread.  The bytes are those of traj_dataset_write_csv (which stays the default writer and the check).
+ *
+ * traj_dataset_format_f64_host / _batch: the formatter alone (csrc/fmt_f64.h: Python's repr(float), NaN as the empty
+ * field) on n doubles, on the host / on the device: value i's characters at out + 24 i (no terminator; at most 24)
+ * and their count in len[i]. */
+int traj_dataset_format_f64_host(const double* v, long long n, char* out /*[n,24]*/, int* len /*[n]*/);
+int traj_dataset_format_f64_batch(const double* v, long long n, char* out /*[n,24]*/, int* len /*[n]*/, void* stream);
+/* Length pass: len[i] = bytes of row row0 + i, its newline included.  total (may be NULL): one device counter the
+ * lengths are added to (the caller zeroes it); the scan of len is the caller's (64-bit offsets). */
+int traj_dataset_csv_device_rows(int which, int B, int T, double Ts, const double* X, const double* U,
+                                 const double* noise, const long long* ids, long long row0, long long nrows,
+                                 int* len /*[nrows]*/, unsigned long long* total, void* stream);
+/* Write pass: row row0 + i goes to out[off[i] - base .. + len[i]), off being byte offsets in the file body (the
+ * exclusive scan of the lengths) and base the offset that out[0] stands for, so a slab of whole rows is written with
+ * base = off[0].  Rows must be contiguous in row order (off[i + 1] = off[i] + len[i]).  Nothing is stored outside
+ * [out, out + out_bytes): a row (or a workgroup's 128 rows) that does not fit there, or whose text is not len[i] bytes
+ * long, is left unwritten and sets *err (a device int the caller zeroes) instead. */
+int traj_dataset_csv_device_format(int which, int B, int T, double Ts, const double* X, const double* U,
+                                   const double* noise, const long long* ids, long long row0, long long nrows,
+                                   const long long* off /*[nrows]*/, const int* len /*[nrows]*/, long long base,
+                                   char* out, long long out_bytes, int* err, void* stream);
+/* Synchronizes `stream` and returns TRAJ_E_LAUNCH if a write pass set *err, TRAJ_OK otherwise. */
+int traj_dataset_csv_device_check(const int* err, void* stream);
+
 /* Data rows (header excluded) and columns of a CSV file; negative TRAJ_E_* on error. */
 long long traj_dataset_csv_rows(const char* path, int* ncols);
 /* All fields of the data rows as float64, row-major [rows, ncols] into out (e.g. pinned host memory);

@@ -158,6 +158,13 @@ _SIGS = {
     "traj_closed_loop_check": (C.c_int, [_V, C.c_size_t, C.c_int, C.c_int, _V]),
     "traj_dataset_write_csv": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double, _V, _V, _V, _V,
                                          C.c_int]),
+    "traj_dataset_format_f64_host": (C.c_int, [_V, C.c_longlong, _V, _V]),
+    "traj_dataset_format_f64_batch": (C.c_int, [_V, C.c_longlong, _V, _V, _V]),
+    "traj_dataset_csv_device_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _V, _V, _V, _V, C.c_longlong,
+                                               C.c_longlong, _V, _V, _V]),
+    "traj_dataset_csv_device_format": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _V, _V, _V, _V, C.c_longlong,
+                                                 C.c_longlong, _V, _V, C.c_longlong, _V, C.c_longlong, _V, _V]),
+    "traj_dataset_csv_device_check": (C.c_int, [_V, _V]),
     "traj_dataset_csv_rows": (C.c_longlong, [C.c_char_p, _V]),
     "traj_dataset_read_csv": (C.c_int, [C.c_char_p, C.c_longlong, C.c_int, _V, C.c_int]),
     "traj_debug_kernel_times": (C.c_int, [_V, _V]),
