@@ -26,8 +26,8 @@
  *     (the reference computes in numpy float64).  Shapes are given per argument.
  *   - `stream` is a hipStream_t (NULL = default stream).  Calls are asynchronous; they never
  *     copy to the host or synchronize, so they can be captured in a hipGraph.  Scratch memory is
- *     always the caller's `workspace` (sizes from traj_mpc_workspace_bytes, plus
- *     traj_mpc_sb_workspace_bytes for the state-bound solver); the library never allocates.
+ *     always the caller's `workspace` (sizes from traj_mpc_step_workspace_bytes, traj_mpc_qp_workspace_bytes
+ *     and traj_closed_loop_workspace_bytes); the library never allocates.
  *   - Return value: 0 on success, negative TRAJ_E_* on argument / launch errors.
  *   - Per-instance solver outcome is written to `status` (TRAJ_STATUS_*, same numbering as the
  *     CVXPY status strings listed below).  Like mpc_6stati.py:257-262, an instance whose status
@@ -72,9 +72,8 @@ typedef struct {
 /* mpc_step keyword arguments (mpc_6stati.py:120-143) + QP solver settings.  Solver defaults are
  * CVXPY's OSQP settings (eps_abs = eps_rel = 1e-5, max_iter = 10000, polish on). */
 typedef struct {
-    int N;                            /* horizon: 1 <= N <= TRAJ_MAX_N for every entry point; the step / QP
-                                       * entry points also take TRAJ_MAX_N < N <= TRAJ_MAX_N_GENERAL (general
-                                       * solver, caller-owned scratch: traj_mpc_sb_workspace_bytes) */
+    int N;                            /* horizon: 1 <= N <= TRAJ_MAX_N_GENERAL for every entry point (the solver
+                                       * by N: "Horizon tiers" below) */
     double Ts;                        /* sampling time */
     double q_c, q_phi, q_vx;          /* :128-131 */
     double R[4], Rd[4];               /* :132-133, 2x2 row-major; the symmetric part is used */
@@ -96,24 +95,30 @@ typedef struct {
                                        * (mpc_6stati.py:256 requests warm_start=True) */
 } traj_mpc_config;
 
-/* Horizon tiers (mpc_step takes any N, mpc_6stati.py:125):
- *   N <= TRAJ_MAX_N (40)                 the register-resident hot kernels (mpc_solve.h): every entry point;
- *   N <= 20                              the one-wave register-resident kernels (mpc_solve.h);
- *   TRAJ_SPLIT_MIN_N <= N <= TRAJ_MAX_N_SPLIT  without state bounds: the row-split kernel (mpc_split.h: K^-1 in registers,
- *                                        each row split across a lane pair joined by v_permlane32_swap, 2 waves per
- *                                        SIMD; the QP entry point keeps the two-wave capacity-80 kernel up to TRAJ_MAX_N);
- *   TRAJ_MAX_N_SPLIT < N <= TRAJ_MAX_N_LONG  without state bounds: the long-horizon kernel (mpc_long.h: the hot kernels'
- *                                        algorithm with one thread per QP variable -- 256 threads, 512 past N = 128 --
- *                                        K^-1 in LDS up to N = 64 and in the caller's scratch beyond);
- *   otherwise (state bounds, or N > TRAJ_MAX_N_LONG up to TRAJ_MAX_N_GENERAL) the general condensed-QP solver
- *                                        (mpc_general.h, one 256-thread workgroup per instance, its Cholesky factor
- *                                        in the caller's scratch).
- * Past TRAJ_MAX_N the step and QP entry points take the scratch of traj_mpc_sb_workspace_bytes; the closed-loop entry
- * points (traj_closed_loop_step / _run) run TRAJ_MAX_N < N <= TRAJ_MAX_N_LONG on the long-horizon kernel, one step per
- * launch sequence (rollout, Jacobians, the closed-loop long-horizon solve with the window, warm rho and plant update),
- * with the same extra scratch after the workspace; with state bounds, or past TRAJ_MAX_N_LONG, they run the general
- * solver, one step per launch sequence, for every N up to TRAJ_MAX_N_GENERAL (traj_closed_loop_workspace_bytes sizes
- * the workspace of every case). */
+/* Horizon tiers (mpc_step takes any N, mpc_6stati.py:125).  Every entry point -- the step, the QP half, the closed
+ * loop per step and fused -- takes every 1 <= N <= TRAJ_MAX_N_GENERAL and picks its solver the same way (one
+ * function, csrc/mpc_route.h):
+ *   state bounds with a finite side, or TRAJ_MAX_N_LONG < N <= TRAJ_MAX_N_GENERAL (257 .. 1024)
+ *                                        the general condensed-QP solver (mpc_general.h, one 256-thread workgroup per
+ *                                        instance, its Cholesky factor in the caller's scratch past TRAJ_MAX_N);
+ *   otherwise TRAJ_MAX_N_SPLIT < N <= TRAJ_MAX_N_LONG (65 .. 256)
+ *                                        the long-horizon kernel (mpc_long.h: the hot kernels' algorithm with one
+ *                                        thread per QP variable -- 256 threads, 512 past N = 128 -- K^-1 in LDS up to
+ *                                        N = 64 and in the caller's scratch beyond);
+ *   otherwise TRAJ_SPLIT_MIN_N <= N <= TRAJ_MAX_N_SPLIT (21 .. 64)
+ *                                        the row-split kernel (mpc_split.h: K^-1 in registers, each row split across
+ *                                        a lane pair joined by v_permlane32_swap, 2 waves per SIMD) -- except that the
+ *                                        QP entry point keeps the two-wave capacity-80 kernel up to TRAJ_MAX_N (40);
+ *   otherwise N <= 20                    the one-wave register-resident kernels (mpc_solve.h).
+ * (traj_debug_split_min_n / _split_max_n move the row-split tier's ends: below it the capacity-80 kernel runs up to
+ * TRAJ_MAX_N, above it the long-horizon kernel.)
+ * The closed loop is fused into one launch (traj_closed_loop_run) on the register-resident and row-split kernels; on
+ * the long-horizon kernel and the general solver it runs one step per launch sequence.
+ * Workspace: ask the entry point's own query -- traj_mpc_step_workspace_bytes, traj_mpc_qp_workspace_bytes,
+ * traj_closed_loop_workspace_bytes.  They are made of traj_mpc_workspace_bytes (every tier up to TRAJ_MAX_N_SPLIT,
+ * the row-split kernel's scratch included) and, for the long-horizon kernel and the general solver, the scratch of
+ * traj_mpc_sb_workspace_bytes after it; so the step and the closed loop need more than traj_mpc_workspace_bytes only
+ * past N = TRAJ_MAX_N_SPLIT (64) or with state bounds. */
 #define TRAJ_MAX_N 40
 #define TRAJ_MAX_N_SPLIT 64      /* TRAJ_SPLIT_MIN_N <= N <= this: the row-split kernel (mpc_split.h), K^-1 rows in
                                   * registers split across lane pairs */
@@ -149,29 +154,32 @@ int traj_lateral_error_batch(int B, const double* X, const double* Y, const doub
  * (B * 4 doubles: rho, valid flag, ADMM iterations, mean iterations of the last fused run), the
  * closed-loop solve order (B ints, longest first) and the fused run's step queue (B + 2 ints).  Pass the same buffer to every traj_closed_loop_step of one run;
  * step t = 0 starts cold.  For TRAJ_SPLIT_MIN_N <= N <= TRAJ_MAX_N_SPLIT the size includes the row-split kernel's scratch.
- * The closed loop at TRAJ_MAX_N_SPLIT < N <= TRAJ_MAX_N_LONG needs traj_mpc_workspace_bytes(B, N) +
- * traj_mpc_sb_workspace_bytes(B, N) bytes (the long-horizon kernel's scratch after the workspace). */
+ * It is what traj_closed_loop_check takes; what an entry point needs is its own query's answer (below). */
 size_t traj_mpc_workspace_bytes(int B, int N);
-/* Scratch of the general solver, which runs with state bounds (x_lo / x_hi given with a finite side,
- * mpc_6stati.py:208-213), and of the long-horizon kernel (every horizon N > TRAJ_MAX_N): B * ~20.5k doubles at
- * N = 20 (N > TRAJ_MAX_N adds the Cholesky factor, 4 N^2 doubles; the long-horizon kernel uses at most 2 (2N + 6)^2).  traj_mpc_step_batch then needs traj_mpc_workspace_bytes(B, N) + this many
- * bytes; traj_mpc_qp_batch this many.  0 for B < 0 or N outside 1 .. TRAJ_MAX_N_GENERAL. */
+/* Scratch of the general solver and of the long-horizon kernel (the same region, after the workspace above):
+ * B * ~20.5k doubles at N = 20 (N > TRAJ_MAX_N adds the Cholesky factor, 4 N^2 doubles; the long-horizon kernel uses
+ * at most 2 (2N + 6)^2).  It is also the whole workspace of traj_mpc_qp_batch wherever that takes one.  0 for B < 0
+ * or N outside 1 .. TRAJ_MAX_N_GENERAL. */
 size_t traj_mpc_sb_workspace_bytes(int B, int N);
+/* What traj_mpc_step_batch / traj_mpc_qp_batch require of `workspace_bytes` for configuration c and B instances, by
+ * the tier c runs on (above): the sizes to allocate by.  0 for a null or invalid configuration or B < 0 (and for the
+ * QP entry on the register-resident kernels, which take no workspace). */
+size_t traj_mpc_step_workspace_bytes(const traj_mpc_config* c, int B);
+size_t traj_mpc_qp_workspace_bytes(const traj_mpc_config* c, int B);
 
 /* ---- the MPC step (mpc_6stati.py:120-275) for B independent instances ----
  * x0 [B,6], u_prev [B,2], path_ref [B,N+1,3], vref [B,N+1]  (vref None / scalar is expanded by the
  * caller, :155-160).  Outputs: u_cmd [B,2], status [B]; optional (may be NULL): objective [B],
  * X_opt [B,6,N+1], U_opt [B,2,N], iters [B] (ADMM iterations), polished [B] (1 if polish accepted).
- * workspace: device buffer of at least traj_mpc_workspace_bytes(B, N) bytes (+ traj_mpc_sb_workspace_bytes(B, N)
- * with state bounds or N > TRAJ_MAX_N). */
+ * workspace: device buffer of at least traj_mpc_step_workspace_bytes(c, B) bytes. */
 int traj_mpc_step_batch(const traj_vehicle_params* p, const traj_mpc_config* c, int B, const double* x0,
                         const double* u_prev, const double* path_ref, const double* vref, double* u_cmd,
                         int* status, double* objective, double* X_opt, double* U_opt, int* iters, int* polished,
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* QP half only (mpc_6stati.py:180-275) with the linearization supplied by the caller:
- * Ad [B,N,6,6], Bd [B,N,6,2], g [B,N,6].  Same outputs as traj_mpc_step_batch.  workspace: only with state
- * bounds or N > TRAJ_MAX_N (>= traj_mpc_sb_workspace_bytes(B, N) bytes), otherwise may be NULL. */
+ * Ad [B,N,6,6], Bd [B,N,6,2], g [B,N,6].  Same outputs as traj_mpc_step_batch.  workspace: at least
+ * traj_mpc_qp_workspace_bytes(c, B) bytes; where that is 0 (no state bounds, N <= TRAJ_MAX_N) it may be NULL. */
 int traj_mpc_qp_batch(const traj_vehicle_params* p, const traj_mpc_config* c, int B, const double* x0,
                       const double* u_prev, const double* path_ref, const double* vref, const double* Ad,
                       const double* Bd, const double* g, double* u_cmd, int* status, double* objective,
@@ -198,8 +206,8 @@ int traj_ref_window_batch(const traj_paths* paths, int B, int N, double Ts, cons
 
 /* Workspace bytes of the closed-loop entry points below for configuration c and B trajectories (every tier: the
  * register-resident and row-split kernels' traj_mpc_workspace_bytes, the long-horizon kernel's scratch after it, and
- * with state bounds the general solver's scratch plus the step's window and u_cmd); 0 for a configuration the closed
- * loop does not take. */
+ * on the general solver its scratch plus the step's window and u_cmd); 0 for a null or invalid configuration or
+ * B < 0. */
 size_t traj_closed_loop_workspace_bytes(const traj_mpc_config* c, int B);
 
 /* One closed-loop step of main.py:85-101 for B trajectories, in place (1 <= N <= TRAJ_MAX_N_GENERAL; with state

@@ -1,0 +1,104 @@
+// san_route.cpp -- csrc/mpc_route.h on the host under AddressSanitizer / UBSan: route() for every horizon -1 .. 1026,
+// with and without state bounds, under the four settings of the row-split switches, for the four entries (B = 1 and 7,
+// the step's linearization switch both ways), held to the invariants the entry points of trajmpc.hip rely on.
+// Prints "san_route ok".
+#include <cstdio>
+#include <cstring>
+
+#include "../../trajectory_generation_amd/csrc/mpc_route.h"
+
+using namespace tgmpc;
+
+static long long checked = 0;
+
+#define REQUIRE(cond)                                                                                            \
+    do {                                                                                                         \
+        if (!(cond)) {                                                                                           \
+            std::printf("san_route FAILED: %s (N=%d bounds=%d split=%d..%d entry=%d B=%d)\n", #cond, c.N, bounds, \
+                        s.split_min_n, s.split_max_n, (int)e, B);                                                \
+            return 1;                                                                                            \
+        }                                                                                                        \
+    } while (0)
+
+static traj_mpc_config config(int N, bool bounds) {
+    traj_mpc_config c;
+    std::memset(&c, 0, sizeof(c));
+    c.N = N;
+    c.Ts = 0.05;
+    c.max_iter = 200;
+    c.check_interval = 25;
+    c.scaling_iters = 10;
+    if (bounds) {   // x_lo given, one finite entry
+        c.has_x_lo = 1;
+        for (int i = 0; i < 6; ++i) c.x_lo[i] = -1e30;
+        c.x_lo[3] = -1.0;
+    }
+    return c;
+}
+
+static int check(const traj_mpc_config& c, bool bounds, const Switches& s, Entry e, int B) {
+    const Route r = route(&c, B, e, s);
+    const int N = c.N;
+    // what check_cfg has always refused: a horizon outside 1 .. TRAJ_MAX_N_GENERAL (the other fields are valid here)
+    REQUIRE((r.err != 0) == (N < 1 || N > TRAJ_MAX_N_GENERAL));
+    ++checked;
+    if (r.err) {
+        REQUIRE(r.err == TRAJ_E_ARG);
+        return 0;
+    }
+    REQUIRE(r.need >= r.scratch_off + r.scratch_bytes);
+    REQUIRE(r.scratch_off % 8 == 0);
+    REQUIRE(r.scratch_off == r.base);
+    REQUIRE((r.base == 0) == (e == Entry::Qp));
+    REQUIRE(r.tier != Tier::Split || (N >= 21 && N <= 64 && !bounds));
+    REQUIRE(r.tier != Tier::Long || (N >= 41 && N <= 256 && !bounds));
+    REQUIRE(r.tier != Tier::Reg || (N <= 40 && !bounds));
+    REQUIRE((r.tier == Tier::General) == (bounds || N > 256));
+    REQUIRE(r.fused == (e == Entry::ClosedRun && (r.tier == Tier::Reg || r.tier == Tier::Split)));
+    REQUIRE(r.inlin == (e == Entry::Step && s.step_inlin && (r.tier == Tier::Reg || r.tier == Tier::Split)));
+    // the scratch holds what the tier's kernel carves from it (split_inst.hip aligns its pointer up to 16 bytes)
+    const size_t B8 = (size_t)B * sizeof(double);
+    if (r.tier == Tier::Split) REQUIRE(r.scratch_bytes >= B8 * split_ws_doubles(N) + 8);
+    if (r.tier == Tier::Long) REQUIRE(r.scratch_bytes >= B8 * long_ws_doubles(N));
+    if (r.tier == Tier::General) REQUIRE(r.scratch_bytes >= B8 * gen_ws_doubles(N));
+    if (r.tier == Tier::Reg) REQUIRE(r.scratch_bytes == 0);
+    // the QP entry keeps the capacity-80 kernel up to TRAJ_MAX_N
+    if (e == Entry::Qp && N <= 40 && !bounds) REQUIRE(r.tier == Tier::Reg && r.need == 0);
+    // the two closed-loop entries share one workspace, never smaller than what traj_closed_loop_check asks for
+    if (e == Entry::ClosedRun) REQUIRE(r.need == route(&c, B, Entry::ClosedStep, s).need);
+    if (e == Entry::ClosedStep) REQUIRE(r.need >= ws_base_bytes(B, N) + split_bytes(B, N));
+    return 0;
+}
+
+int main() {
+    const int pairs[4][2] = {{21, 64}, {41, 64}, {21, 0}, {41, 0}};
+    const Entry entries[4] = {Entry::Step, Entry::Qp, Entry::ClosedStep, Entry::ClosedRun};
+    const int batches[2] = {1, 7};
+    for (int N = -1; N <= 1026; ++N)
+        for (int bounds = 0; bounds < 2; ++bounds)
+            for (const auto& pr : pairs)
+                for (int inlin = 0; inlin < 2; ++inlin)
+                    for (Entry e : entries)
+                        for (int B : batches) {
+                            const traj_mpc_config c = config(N, bounds);
+                            if (check(c, bounds, Switches{pr[0], pr[1], inlin}, e, B)) return 1;
+                        }
+    // refused whatever the horizon: no configuration, B < 0, an invalid field
+    const Switches s{21, 64, 1};
+    traj_mpc_config c = config(20, false);
+    if (route(nullptr, 4, Entry::Step, s).err != TRAJ_E_ARG || route(&c, -1, Entry::Step, s).err != TRAJ_E_ARG ||
+        route(&c, 0, Entry::Step, s).err != TRAJ_OK) {
+        std::printf("san_route FAILED: null configuration / B\n");
+        return 1;
+    }
+    c.Ts = 0.0;
+    traj_mpc_config c2 = config(20, false);
+    c2.polish_mode = 2;
+    for (Entry e : entries)
+        if (route(&c, 4, e, s).err != TRAJ_E_ARG || route(&c2, 4, e, s).err != TRAJ_E_ARG) {
+            std::printf("san_route FAILED: invalid field accepted\n");
+            return 1;
+        }
+    std::printf("san_route ok: %lld routes\n", checked);
+    return 0;
+}

@@ -238,6 +238,114 @@ def test_argument_errors_are_reported_before_any_launch(L):
                   nul) == _lib.TRAJ_E_ARG
 
 
+ROUTE_GOLDEN = os.path.join(ROOT, "tests", "golden", "route_parent.npz")
+
+
+def _route_cfg(N, bounds):
+    """tests/golden/gen_route_parent.py's configuration: the default one; bounds = x_lo with one finite entry."""
+    c = _lib.default_config(int(N), 0.05)
+    if bounds:
+        c.has_x_lo = 1
+        for i in range(6):
+            c.x_lo[i] = -1e30
+        c.x_lo[3] = -1.0
+    return c
+
+
+@pytest.fixture
+def route_switches(L):
+    """Sets (traj_debug_split_min_n, traj_debug_split_max_n); the library's defaults are back afterwards."""
+    def set_(mn, mx):
+        assert L.traj_debug_split_min_n(int(mn)) == _lib.TRAJ_OK and L.traj_debug_split_max_n(int(mx)) == _lib.TRAJ_OK
+    yield set_
+    set_(_lib.SPLIT_MIN_N, _lib.MAX_N_SPLIT)
+
+
+def test_routing_sizes_equal_the_parents(L, route_switches):
+    """csrc/mpc_route.h decides the solver tier and sizes every workspace; the sizes the three public queries return
+    are those of the commit before it (route_parent.npz, recorded by tests/golden/gen_route_parent.py): every N in
+    0..1025, B in {1, 7}, with and without state bounds, under the four settings of the row-split switches."""
+    g = np.load(ROUTE_GOLDEN)
+    Ns, Bs = g["N"], g["B"]
+    assert (Ns[0], Ns[-1], len(Ns)) == (0, 1025, 1026) and list(Bs) == [1, 7] and len(g["switches"]) == 4
+    for bi, B in enumerate(Bs):
+        assert [L.traj_mpc_workspace_bytes(int(B), int(N)) for N in Ns] == g["workspace"][bi].tolist()
+        assert [L.traj_mpc_sb_workspace_bytes(int(B), int(N)) for N in Ns] == g["sb_workspace"][bi].tolist()
+    for si, (mn, mx) in enumerate(g["switches"]):
+        route_switches(mn, mx)
+        for bounds in (0, 1):
+            cfgs = [_route_cfg(N, bounds) for N in Ns]
+            for bi, B in enumerate(Bs):
+                got = [L.traj_closed_loop_workspace_bytes(C.byref(c), int(B)) for c in cfgs]
+                assert got == g["closed"][si, bounds, bi].tolist(), (mn, mx, bounds, B)
+
+
+def test_step_and_qp_workspace_queries(L, route_switches):
+    """traj_mpc_step_workspace_bytes / traj_mpc_qp_workspace_bytes over the same table, against the sizes the entry
+    points required before the queries existed, written out from the public pieces: the step's base part, then the
+    general solver's scratch (state bounds, or past TRAJ_MAX_N off the row-split kernel) or the row-split kernel's;
+    the QP entry the general solver's scratch with state bounds or past TRAJ_MAX_N, else nothing."""
+    def base(B, N):
+        return (B * N * 66 + 4 * B) * 8 + ((4 * (3 * B + 2) + 7) // 8) * 8
+
+    def split_bytes(B, N):
+        if not (_lib.SPLIT_MIN_N <= N <= _lib.MAX_N_SPLIT):
+            return 0
+        H = 40 if 2 * N <= 80 else (48 if 2 * N <= 96 else 64)
+        return (B * 32 * ((2 * H + 31) // 32) * 2 * H + 2) * 8
+
+    g = np.load(ROUTE_GOLDEN)
+    for mn, mx in g["switches"]:
+        route_switches(mn, mx)
+        for bounds in (0, 1):
+            for N in g["N"]:
+                N = int(N)
+                c = _route_cfg(N, bounds)
+                for bi, B in enumerate(g["B"]):
+                    B = int(B)
+                    if not 1 <= N <= _lib.MAX_N_GENERAL:
+                        want_step = want_qp = 0
+                    else:
+                        sb = int(g["sb_workspace"][bi, N])
+                        split = not bounds and mn <= N <= mx
+                        gen_long = bounds or (N > _lib.MAX_N and not split)
+                        want_step = base(B, N) + (sb if gen_long else split_bytes(B, N) if split else 0)
+                        want_qp = sb if bounds or N > _lib.MAX_N else 0
+                    assert L.traj_mpc_step_workspace_bytes(C.byref(c), B) == want_step, (mn, mx, bounds, N, B)
+                    assert L.traj_mpc_qp_workspace_bytes(C.byref(c), B) == want_qp, (mn, mx, bounds, N, B)
+    c = _lib.default_config(20, 0.05)
+    for q in (L.traj_mpc_step_workspace_bytes, L.traj_mpc_qp_workspace_bytes):
+        assert q(None, 4) == 0 and q(C.byref(c), -1) == 0
+    c.Ts = 0.0
+    assert L.traj_mpc_step_workspace_bytes(C.byref(c), 4) == 0
+
+
+def test_each_tier_refuses_a_workspace_short_of_its_query(L):
+    """One horizon per tier and entry point: 8 bytes less than the entry's own query is an argument error before any
+    launch (only sizes that must be refused are passed: the pointers are fake)."""
+    p = _lib.default_params()
+    nul, fake = None, C.c_void_p(16)
+    ps = _lib.Paths()
+    ps.kmax, ps.kind, ps.pc = 0, 16, 16
+    B = 4
+    for N, bounds in ((20, 0), (24, 0), (41, 0), (64, 0), (65, 0), (129, 0), (257, 0), (20, 1)):
+        c = _route_cfg(N, bounds)
+        need = L.traj_mpc_step_workspace_bytes(C.byref(c), B)
+        assert need >= L.traj_mpc_workspace_bytes(B, N) > 0
+        assert L.traj_mpc_step_batch(C.byref(p), C.byref(c), B, *([fake] * 11), fake, need - 8, nul) == _lib.TRAJ_E_ARG
+        need = L.traj_mpc_qp_workspace_bytes(C.byref(c), B)
+        assert (need == 0) == (N <= _lib.MAX_N and not bounds)   # the register-resident kernels take no scratch
+        if need:
+            assert L.traj_mpc_qp_batch(C.byref(p), C.byref(c), B, *([fake] * 14), fake, need - 8,
+                                       nul) == _lib.TRAJ_E_ARG
+        need = L.traj_closed_loop_workspace_bytes(C.byref(c), B)
+        assert need >= L.traj_mpc_workspace_bytes(B, N) > 0
+        assert L.traj_closed_loop_step(C.byref(p), C.byref(c), C.byref(ps), B, fake, fake, fake, 0, 0, nul, nul, nul,
+                                       nul, fake, need - 8, nul) == _lib.TRAJ_E_ARG
+        assert L.traj_closed_loop_run(C.byref(p), C.byref(c), C.byref(ps), B, fake, fake, fake, 0, 1, 0, nul, nul, nul,
+                                      nul, fake, need - 8, nul) == _lib.TRAJ_E_ARG
+
+
 def test_check_raises():
     with pytest.raises(RuntimeError):
         _lib.check(_lib.TRAJ_E_ARG, "x")

@@ -19,6 +19,7 @@ oracle's on all stages where both polished, 1e-5 (1 + |X|) -- 10 x the U bar, th
 C: both with non-default weights (off-diagonal R / Rd), asymmetric boxes, q_* and vehicle parameters, plus parity with
 the oracle under the same settings; a non-symmetric R gives the symmetrized R's outputs bit for bit.
 D: batch independence and determinism past N = 20 (row-split, long, general).
+E: every tier's entry points on a workspace of exactly the size their query returns, a guard behind it untouched.
 
 Measured on an MI355X, worst error / bar with C = 1 (the CPU oracle's in brackets): X 0.108 (0.108), objective 0.152
 (0.0847), violation 0.94 of the eps bar / 0.018 of 1e-9, optimality gap 5.0e-10, step-entry X_opt against the oracle's
@@ -184,3 +185,105 @@ def test_batch_independence_past_n20(gpu, N, bounds):
             d = TB.mpc_step_batch(x0[i:i + 1], up[i:i + 1], pr[i:i + 1], vr[i:i + 1], cfg)
             for k in a:
                 assert _same(a[k][i:i + 1], d[k]), (mode, "B = 1", i, k)
+
+
+# ---- E: every tier on exactly the workspace its query asks for
+
+GUARD_BYTES, GUARD_FILL = 4096, 0xA5
+
+
+def _guarded_workspace(need, dev):
+    """`need` zeroed bytes followed by a 4 KiB guard of a fixed bit pattern."""
+    buf = torch.zeros(need + GUARD_BYTES, dtype=torch.uint8, device=dev)
+    buf[need:] = GUARD_FILL
+    return buf
+
+
+def _guard_intact(buf, need):
+    torch.cuda.synchronize()
+    return bool((buf[need:] == GUARD_FILL).all())
+
+
+@contextlib.contextmanager
+def _split_min_n(n_min):
+    prev = TB.SPLIT_MIN_N
+    if n_min is not None:
+        TB.set_split_min_n(n_min)
+    try:
+        yield
+    finally:
+        TB.set_split_min_n(prev)
+
+
+TIER_CASES = [("reg-N20", 20, {}, None), ("split-N24", 24, {}, None), ("cap80-N24", 24, {}, 41),
+              ("split-N41", 41, {}, None), ("split-N64", 64, {}, None), ("long-N65", 65, {}, None),
+              ("long-N130", 130, {}, None), ("general-N20-vx", 20, M.SETTINGS["vx"][0], None)]
+
+
+@pytest.mark.parametrize("name,N,kw,min_n", TIER_CASES, ids=[c[0] for c in TIER_CASES])
+def test_step_and_closed_step_on_exactly_the_queried_workspace(gpu, name, N, kw, min_n):
+    """E: traj_mpc_step_workspace_bytes / traj_closed_loop_workspace_bytes are what the entry points use, per tier
+    (csrc/mpc_route.h).  The C entry point called directly on a workspace of exactly the queried size leaves the 4 KiB
+    guard behind it untouched, and its outputs are those of the batch API on the same inputs, bit for bit."""
+    import ctypes as C
+
+    from trajectory_generation_amd import _lib
+    L, p, B, Ts = _lib.lib(), _lib.default_params(), 3, 0.05
+    cfg = TB.config_struct(N=N, Ts=Ts, max_iter=200, **kw)
+    x0, up, pr, vr = (TB._dev(a) for a in random_instances(11, B, N, Ts))
+    with _split_min_n(min_n):
+        # the step
+        ref = TB.mpc_step_batch(x0, up, pr, vr, cfg)
+        need = int(L.traj_mpc_step_workspace_bytes(C.byref(cfg), B))
+        assert need > 0
+        ws, o = _guarded_workspace(need, gpu), TB._outputs(B, N, gpu)
+        _lib.check(L.traj_mpc_step_batch(
+            C.byref(p), C.byref(cfg), B, TB._p(x0), TB._p(up), TB._p(pr), TB._p(vr), TB._p(o["u_cmd"]),
+            TB._p(o["status"]), TB._p(o["objective"]), TB._p(o["X_opt"]), TB._p(o["U_opt"]), TB._p(o["iters"]),
+            TB._p(o["polished"]), TB._p(ws), need, TB._stream()), "traj_mpc_step_batch")
+        assert _guard_intact(ws, need), (name, "step")
+        assert (o["iters"] > 0).all() and (o["status"] >= 0).all() and (o["status"] <= 6).all(), (o["iters"], o["status"])
+        for k in ref:
+            assert _same(ref[k], o[k]), (name, "step", k)
+        # one closed-loop step from the same states (t = 0: cold, nothing read from the workspace)
+        xy = x0[:, :2].cpu().numpy()   # (parabolas through the states' positions)
+        paths = TB.PathSet.build([0] * B, [[y - 0.1 * x * x, 0.0, 0.1, 0.0] for x, y in xy])
+        xa, ua, xb, ub = x0.clone(), up.clone(), x0.clone(), up.clone()
+        sta, stb = (torch.full((B,), -1, dtype=torch.int32, device=gpu) for _ in range(2))
+        TB.closed_loop_step(xa, ua, paths, vr, cfg, status=sta)
+        need = int(L.traj_closed_loop_workspace_bytes(C.byref(cfg), B))
+        assert need > 0
+        ws, ps = _guarded_workspace(need, gpu), paths.struct()
+        _lib.check(L.traj_closed_loop_step(
+            C.byref(p), C.byref(cfg), C.byref(ps), B, TB._p(xb), TB._p(ub), TB._p(vr), 0, 0, None, None, TB._p(stb),
+            None, TB._p(ws), need, TB._stream()), "traj_closed_loop_step")
+        assert _guard_intact(ws, need), (name, "closed-loop step")
+        assert (stb >= 0).all() and (stb <= 6).all(), stb
+        assert not torch.equal(xb, x0)
+        assert torch.equal(xa, xb) and torch.equal(ua, ub) and torch.equal(sta, stb), (name, "closed-loop step")
+
+
+@pytest.mark.parametrize("N", [40, 41], ids=["cap80-N40", "split-N41"])
+def test_qp_entry_on_exactly_the_queried_workspace(gpu, N):
+    """E for the QP entry: at N = 40 it keeps the capacity-80 kernel and takes no workspace (a guard alone is passed,
+    with size 0); at N = 41 the row-split kernel runs on traj_mpc_qp_workspace_bytes.  The linearization is the one at
+    (x0, u_prev), repeated over the horizon."""
+    import ctypes as C
+
+    from trajectory_generation_amd import _lib
+    L, p, B, Ts = _lib.lib(), _lib.default_params(), 3, 0.05
+    cfg = TB.config_struct(N=N, Ts=Ts, max_iter=200)
+    x0, up, pr, vr = (TB._dev(a) for a in random_instances(12, B, N, Ts))
+    lin = [a.unsqueeze(1).expand(B, N, *a.shape[1:]).contiguous() for a in TB.linearize_discretize_batch(x0, up, Ts)]
+    ref = TB.mpc_qp_batch(x0, up, pr, vr, *lin, cfg)
+    need = int(L.traj_mpc_qp_workspace_bytes(C.byref(cfg), B))
+    assert (need == 0) == (N == 40)
+    ws, o = _guarded_workspace(need, gpu), TB._outputs(B, N, gpu)
+    _lib.check(L.traj_mpc_qp_batch(
+        C.byref(p), C.byref(cfg), B, TB._p(x0), TB._p(up), TB._p(pr), TB._p(vr), *[TB._p(a) for a in lin],
+        TB._p(o["u_cmd"]), TB._p(o["status"]), TB._p(o["objective"]), TB._p(o["X_opt"]), TB._p(o["U_opt"]),
+        TB._p(o["iters"]), TB._p(o["polished"]), TB._p(ws), need, TB._stream()), "traj_mpc_qp_batch")
+    assert _guard_intact(ws, need), N
+    assert (o["iters"] > 0).all() and (o["status"] >= 0).all() and (o["status"] <= 6).all(), (o["iters"], o["status"])
+    for k in ref:
+        assert _same(ref[k], o[k]), (N, k)

@@ -1,6 +1,6 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer runs of the host C / C++ code (sanitizers),
-on the CPU: the product path's CSV writer / reader (trajectory_generation_amd/csrc/dataset_csv.cpp) and the C oracle
-(oracle/traj_oracle.c, riccati_ipm.c), each driven by a harness under tests/sanitize/ and built with
+on the CPU: the product path's CSV writer / reader (trajectory_generation_amd/csrc/dataset_csv.cpp), the MPC routing
+header (csrc/mpc_route.h) and the C oracle (oracle/traj_oracle.c, riccati_ipm.c), each driven by a harness under tests/sanitize/ and built with
 -fsanitize=address,undefined -fno-sanitize-recover (any report fails the run; leaks are reported at exit).  The
 GPU kernels are out of reach here: GPU sanitizers are not available on this pool."""
 import os
@@ -30,6 +30,16 @@ def test_dataset_csv_under_asan_ubsan(tmp_path):
           os.path.join(HERE, "sanitize", "san_csv.cpp")])
     r = _run([exe, str(tmp_path)], env=ENV)
     assert "san_csv ok" in r.stdout and "ERROR" not in r.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_mpc_route_under_asan_ubsan(tmp_path):
+    """csrc/mpc_route.h (the MPC solver tier and workspace sizes, host-only) alone under g++: its invariants over
+    every horizon, state bounds, switch setting and entry."""
+    exe = str(tmp_path / "san_route")
+    _run(["g++", *SAN, "-std=c++17", "-Wall", "-Werror", "-o", exe, os.path.join(HERE, "sanitize", "san_route.cpp")])
+    r = _run([exe], env=ENV)
+    assert "san_route ok" in r.stdout and "ERROR" not in r.stderr
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")

@@ -18,7 +18,7 @@ HEADERS = [HEADER, os.path.join(os.path.dirname(_HERE), "include", "trajknet.h")
            os.path.join(os.path.dirname(_HERE), "include", "trajgen.h")]
 
 TRAJ_OK, TRAJ_E_ARG, TRAJ_E_UNSUPPORTED, TRAJ_E_LAUNCH, TRAJ_E_HANDOFF = 0, -1, -2, -3, -4
-MAX_N = 40            # hot kernels, every entry point (include/trajmpc.h TRAJ_MAX_N)
+MAX_N = 40            # the register-resident hot kernels' capacity (include/trajmpc.h TRAJ_MAX_N)
 MAX_N_SPLIT = 64      # the row-split kernel for SPLIT_MIN_N <= N <= MAX_N_SPLIT (TRAJ_MAX_N_SPLIT)
 SPLIT_MIN_N = 21      # TRAJ_SPLIT_MIN_N
 MAX_N_LONG = 256      # step / QP entry points on the long-horizon kernel without state bounds (TRAJ_MAX_N_LONG)
@@ -138,6 +138,8 @@ _SIGS = {
     "traj_lateral_error_batch": (C.c_int, [C.c_int, _V, _V, _V, _V, _V, _V, _V]),
     "traj_mpc_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "traj_mpc_sb_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "traj_mpc_step_workspace_bytes": (C.c_size_t, [C.POINTER(MpcConfig), C.c_int]),
+    "traj_mpc_qp_workspace_bytes": (C.c_size_t, [C.POINTER(MpcConfig), C.c_int]),
     "traj_closed_loop_workspace_bytes": (C.c_size_t, [C.POINTER(MpcConfig), C.c_int]),
     "traj_mpc_step_batch": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.c_int, _V, _V, _V, _V,
                                       _V, _V, _V, _V, _V, _V, _V, _V, C.c_size_t, _V]),

@@ -274,38 +274,28 @@ def _outputs(B, N, device):
 _WS = {}
 
 
-def _state_bounds(cfg: MpcConfig) -> bool:
-    """x_lo / x_hi given with a finite side (mpc_6stati.py:208-213): the general solver runs."""
-    return any((cfg.has_x_lo and cfg.x_lo[i] > -1e30) or (cfg.has_x_hi and cfg.x_hi[i] < 1e30) for i in range(6))
-
-
 # horizons from which the row-split kernel runs (traj_debug_split_min_n; the library default TRAJ_SPLIT_MIN_N)
 SPLIT_MIN_N = _lib.SPLIT_MIN_N
 
 
 def set_split_min_n(n_min: int) -> None:
     """Experiments: run the row-split kernel from horizon n_min on (step and closed loop; 21 .. MAX_N + 1, the latter
-    sending 20 < N <= MAX_N back to the capacity-80 kernel).  The workspace sizes do not depend on it."""
+    sending 20 < N <= MAX_N back to the capacity-80 kernel).  traj_mpc_workspace_bytes does not depend on it."""
     global SPLIT_MIN_N
     _lib.check(_lib.lib().traj_debug_split_min_n(int(n_min)), "traj_debug_split_min_n")
     SPLIT_MIN_N = int(n_min)
 
 
-def _general(cfg: MpcConfig) -> bool:
-    """The step needs caller-owned scratch (traj_mpc_sb_workspace_bytes): state bounds, or a horizon past the hot
-    kernels' capacity (MAX_N < N <= MAX_N_GENERAL, include/trajmpc.h's tiers) or routed to the row-split kernel."""
-    return _state_bounds(cfg) or cfg.N > _lib.MAX_N
-
-
-def workspace(B: int, N: int, device, extra_bytes: int = 0, role: str = "closed_loop") -> torch.Tensor:
-    """Cached device workspace for B instances of horizon N (traj_mpc_workspace_bytes), plus extra_bytes
-    (traj_mpc_sb_workspace_bytes: the state-bound solver's scratch, caller-owned like the rest).
+def sized_workspace(nbytes: int, device, role: str = "closed_loop") -> torch.Tensor:
+    """Cached device workspace of at least nbytes: what the entry point's own query returns for the configuration and
+    batch (traj_mpc_step_workspace_bytes, traj_mpc_qp_workspace_bytes, traj_closed_loop_workspace_bytes).  The library
+    decides the solver tier and sizes its scratch (csrc/mpc_route.h); nothing here restates that.
 
     One buffer per (device, stream, role).  The closed loop keeps state in its workspace between calls (the
     warm-start records, the previous launch's order, the step queue), so the one-shot step / QP entry points
     use a buffer of their own ("step"): a state-bound solve between two closed-loop steps on the same stream
     must not overwrite -- or, by growing the cache, replace -- the closed loop's buffer."""
-    nbytes = int(_lib.lib().traj_mpc_workspace_bytes(int(B), int(N))) + int(extra_bytes)
+    nbytes = int(nbytes)
     key = (str(device), torch.cuda.current_stream(device).cuda_stream, role)
     ws = _WS.get(key)
     if ws is None or ws.numel() * 8 < nbytes:
@@ -315,6 +305,11 @@ def workspace(B: int, N: int, device, extra_bytes: int = 0, role: str = "closed_
         ws = new
         _WS[key] = ws
     return ws
+
+
+def workspace(B: int, N: int, device, extra_bytes: int = 0, role: str = "closed_loop") -> torch.Tensor:
+    """sized_workspace of traj_mpc_workspace_bytes(B, N) + extra_bytes (the closed loop's: _closed_extra)."""
+    return sized_workspace(int(_lib.lib().traj_mpc_workspace_bytes(int(B), int(N))) + int(extra_bytes), device, role)
 
 
 def mpc_step_batch(x0, u_prev, path_ref, vref, cfg: MpcConfig, params=None, out: dict | None = None) -> dict:
@@ -331,8 +326,7 @@ def mpc_step_batch(x0, u_prev, path_ref, vref, cfg: MpcConfig, params=None, out:
     path_ref = _dev(path_ref, (B, N + 1, 3), dev)
     vref = _dev(vref, (B, N + 1), dev)
     o = out if out is not None else _outputs(B, N, dev)
-    sb = int(_lib.lib().traj_mpc_sb_workspace_bytes(B, N)) if _general(cfg) else 0
-    ws = workspace(B, N, dev, sb, role="step")
+    ws = sized_workspace(_lib.lib().traj_mpc_step_workspace_bytes(C.byref(cfg), B), dev, role="step")
     _lib.check(_lib.lib().traj_mpc_step_batch(
         C.byref(params_struct(params)), C.byref(cfg), B, _p(x0), _p(u_prev), _p(path_ref), _p(vref),
         _p(o["u_cmd"]), _p(o["status"]), _p(o["objective"]), _p(o["X_opt"]), _p(o["U_opt"]), _p(o["iters"]),
@@ -349,12 +343,12 @@ def mpc_qp_batch(x0, u_prev, path_ref, vref, Ad, Bd, g, cfg: MpcConfig, params=N
     args = [_dev(u_prev, (B, 2), dev), _dev(path_ref, (B, N + 1, 3), dev), _dev(vref, (B, N + 1), dev),
             _dev(Ad, (B, N, 6, 6), dev), _dev(Bd, (B, N, 6, 2), dev), _dev(g, (B, N, 6), dev)]
     o = _outputs(B, N, dev)
-    sb = int(_lib.lib().traj_mpc_sb_workspace_bytes(B, N)) if _general(cfg) else 0
-    ws = workspace(0, N, dev, sb, role="step") if sb else None
+    need = int(_lib.lib().traj_mpc_qp_workspace_bytes(C.byref(cfg), B))
+    ws = sized_workspace(need, dev, role="step") if need else None   # (the register-resident kernels take none)
     _lib.check(_lib.lib().traj_mpc_qp_batch(
         C.byref(params_struct(params)), C.byref(cfg), B, _p(x0), *[_p(a) for a in args],
         _p(o["u_cmd"]), _p(o["status"]), _p(o["objective"]), _p(o["X_opt"]), _p(o["U_opt"]), _p(o["iters"]),
-        _p(o["polished"]), _p(ws) if ws is not None else None, sb, _stream()), "traj_mpc_qp_batch")
+        _p(o["polished"]), _p(ws) if ws is not None else None, need, _stream()), "traj_mpc_qp_batch")
     return o
 
 
@@ -456,9 +450,8 @@ def ref_window_batch(paths: PathSet, x_start, vref, N, Ts) -> torch.Tensor:
 
 
 def _closed_extra(B: int, cfg: MpcConfig) -> int:
-    """Bytes the closed loop needs past traj_mpc_workspace_bytes (traj_closed_loop_workspace_bytes): the long-horizon
-    kernel's scratch (MAX_N_SPLIT < N <= MAX_N_LONG), or with state bounds the general solver's plus the step's window
-    and u_cmd (one step per launch sequence, as the step entry point)."""
+    """Bytes the closed loop needs past traj_mpc_workspace_bytes, by traj_closed_loop_workspace_bytes: the scratch of
+    the long-horizon kernel or the general solver (with its window and u_cmd) where cfg runs on one of them."""
     L = _lib.lib()
     need = int(L.traj_closed_loop_workspace_bytes(C.byref(cfg), int(B)))
     return max(0, need - int(L.traj_mpc_workspace_bytes(int(B), int(cfg.N))))

@@ -1785,7 +1785,6 @@ int traj_knet_fc2_f32(const traj_knet_net* net, int B, const float* x2, float* w
     if (!x2 || !ws || ws_bytes < traj_knet_fc2_workspace_bytes(net, B) || ((uintptr_t)x2 & 15) ||
         ((uintptr_t)net->fc2a_w & 15) || ((uintptr_t)net->fc2a_b & 15) || ((uintptr_t)net->fc2b_w & 15))
         return TRAJ_E_ARG;
-    const int hs = fc2_slab(net->d_fc2h), nslab = net->d_fc2h / hs, nbb = nblk(B, F2_BT);
     return fc2_launch(net, B, x2, ws, stream);
 }
 

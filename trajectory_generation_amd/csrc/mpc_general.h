@@ -23,23 +23,16 @@
 // the 4096-trajectory closed loop never takes it.
 #pragma once
 #include "mpc_common.h"
+#include "mpc_sizes.h"   // gen_ws_doubles, GEN_NMAX
 
 namespace tgmpc {
 
 constexpr int GEN_NT = 256;
-constexpr int GEN_NMAX = 2 * TRAJ_MAX_N;                    // n whose Cholesky factor is kept in LDS
 // rows per lane of the one-wave triangular solves (a register array): the kernel is instantiated for n <= 512 (8 rows
-// per lane, every horizon up to N = 256) and for n <= 2 TRAJ_MAX_N_GENERAL (launch_general picks by n)
+// per lane, every horizon up to N = 256) and for n <= 2 TRAJ_MAX_N_GENERAL (launch_gen picks by n)
 constexpr int GEN_RMAX_SMALL = 8;
 constexpr int GEN_RMAX = (2 * TRAJ_MAX_N_GENERAL + 63) / 64;
 static_assert(GEN_RMAX >= GEN_RMAX_SMALL, "two instances");
-
-// per-instance scratch of solve_gen_kernel, in doubles (m <= 10 N rows; n > GEN_NMAX: + the n x n factor)
-__host__ __device__ inline size_t gen_ws_doubles(int N) {
-    const size_t n = 2 * (size_t)N, m = 10 * (size_t)N;
-    return n * n + m * n + 6 * (size_t)(N + 1) * n + 6 * (size_t)(N + 1) + 3 * n + 20 * n + 24 * m + 64 +
-           (n > (size_t)GEN_NMAX ? n * n : 0);
-}
 
 struct GenWs {
     double *L;   // the Cholesky factor when it does not fit LDS (n > GEN_NMAX), else null

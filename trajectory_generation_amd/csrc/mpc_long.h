@@ -24,19 +24,13 @@
 // LDS buffers.
 #pragma once
 #include "mpc_common.h"
+#include "mpc_sizes.h"   // long_ld, long_ws_doubles, LONG_NKL
 
 namespace tgmpc {
 
 constexpr int LONG_NT = 256;                  // threads per instance = max n (n <= 256)
 constexpr int LONG_NT2 = 512;                 // the instance for 256 < n <= 512 (round 6: N up to 256)
-constexpr int LONG_NKL = 128;                 // n up to which K^-1 lives in LDS
 
-__host__ __device__ inline int long_ld(int n) { return (n + 7) & ~7; }
-// per-instance scratch (doubles): P, and K^-1 when it does not fit LDS
-__host__ __device__ inline size_t long_ws_doubles(int N) {
-    const int n = 2 * N, ld = long_ld(n);
-    return (size_t)ld * ld * (n > LONG_NKL ? 2 : 1);
-}
 __host__ inline size_t long_lds_bytes(int N) {
     const int n = 2 * N;
     return n <= LONG_NKL ? (size_t)long_ld(n) * long_ld(n) * sizeof(double) : 0;

@@ -25,6 +25,7 @@
 #pragma once
 #include "mpc_common.h"
 #include "mpc_linearize.h"
+#include "mpc_sizes.h"   // split_h, split_ws_doubles
 
 namespace tgmpc {
 
@@ -35,12 +36,6 @@ template <int H> struct SplitCfg {
     static constexpr int NT = 64 * WAVES;
     static constexpr int NRW = 32 * WAVES;           // row slots (>= NR)
 };
-__host__ __device__ inline int split_h(int n) { return n <= 80 ? 40 : (n <= 96 ? 48 : 64); }
-// per-instance scratch (doubles): the scaled P, NRW rows x 2H
-__host__ __device__ inline size_t split_ws_doubles(int N) {
-    const int H = split_h(2 * N);
-    return (size_t)(32 * ((2 * H + 31) / 32)) * (2 * H);
-}
 
 // partner lane's value (lane ^ 32) and the pair sum (the same bits on both lanes)
 __device__ __forceinline__ void swap32(double v, double& mine_lo_half, double& mine_hi_half) {

@@ -1,6 +1,7 @@
 // split_inst.hip -- the row-split kernel's instantiations (mpc_split.h) and their launches, in a translation unit of
 // their own so that it is compiled like the other register-resident solvers (no machine-level LICM: hoisting per-lane
 // values out of the sweep and ADMM loops keeps them live across the whole solve and spills).
+#include <atomic>
 #include <cstdint>
 
 #include "mpc_split.h"
@@ -37,20 +38,21 @@ static int launch_split_t(const KArgs& a, double* sws, hipStream_t st) {
 // the slot count is asked of the occupancy API once.
 template <int H>
 static int launch_fused_h(const KArgs& a, double* al, size_t per, hipStream_t st) {
-    static int slots_per_cu[64] = {0};
-    static int cus[64] = {0};
+    // (atomics, as launch_long's attribute flags: concurrent callers on several host threads at worst ask twice)
+    static std::atomic<int> slots[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -3;
-    if (!slots_per_cu[dev]) {
+    int nslots = slots[dev].load(std::memory_order_acquire);
+    if (!nslots) {
         int nb = 0, ncu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_split_kernel<H, true, true>, SplitCfg<H>::NT, 0) !=
                 hipSuccess ||
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
             return -3;
-        slots_per_cu[dev] = nb < 1 ? 1 : nb;
-        cus[dev] = ncu < 1 ? 1 : ncu;
+        nslots = (nb < 1 ? 1 : nb) * (ncu < 1 ? 1 : ncu);
+        slots[dev].store(nslots, std::memory_order_release);
     }
-    int G = a.fused_grid > 0 ? a.fused_grid : slots_per_cu[dev] * cus[dev];
+    int G = a.fused_grid > 0 ? a.fused_grid : nslots;
     if (G > a.B) G = a.B;
     const int minG = (a.B + TRAJ_FUSED_MAX_PER_WG - 1) / TRAJ_FUSED_MAX_PER_WG;
     if (G < minG) G = minG;

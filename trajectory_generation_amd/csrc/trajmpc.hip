@@ -14,7 +14,8 @@
 #include "mpc_common.h"
 #include "mpc_general.h"
 #include "mpc_long.h"
-#include "mpc_split.h"   // (split_ws_doubles; the kernels are instantiated in split_inst.hip)
+#include "mpc_split.h"   // (the kernels are instantiated in split_inst.hip)
+#include "mpc_route.h"
 #include "mpc_linearize.h"
 #include "physics.h"
 
@@ -204,30 +205,11 @@ static int launch_mpc(const KArgs& a, hipStream_t st, int mode) {
     return TRAJ_E_ARG;
 }
 
-// state bounds (mpc_6stati.py:208-213) with at least one finite side
-static bool state_bounds_active(const traj_mpc_config* c) {
-    for (int i = 0; i < 6; ++i) {
-        if (c->has_x_lo && c->x_lo[i] > -INFTY) return true;
-        if (c->has_x_hi && c->x_hi[i] < INFTY) return true;
-    }
-    return false;
-}
-
-// allow_sb: the caller can run the general solver (state bounds, horizons past TRAJ_MAX_N); the closed-loop
-// entry points cannot
-static int check_cfg(const traj_mpc_config* c, bool allow_sb = false) {
-    if (!c) return TRAJ_E_ARG;
-    if (c->N < 1 || c->N > TRAJ_MAX_N_GENERAL) return TRAJ_E_ARG;
-    if (c->N > TRAJ_MAX_N && !allow_sb) return TRAJ_E_UNSUPPORTED;
-    if (!(c->Ts > 0.0) || c->max_iter < 1 || c->check_interval < 1 || c->scaling_iters < 0) return TRAJ_E_ARG;
-    if (c->polish_mode != 0 && c->polish_mode != 1) return TRAJ_E_ARG;
-    if (!allow_sb && state_bounds_active(c)) return TRAJ_E_UNSUPPORTED;
-    return TRAJ_OK;
-}
+static_assert(BOUND_INF == INFTY, "mpc_route.h reads the state bounds as the kernels do");
 
 // the general solver (mpc_general.h) for configurations with state bounds: its per-instance scratch is
 // the caller's (traj_mpc_sb_workspace_bytes), like every other buffer -- no allocation per call
-static int launch_general(const KArgs& a, double* gws, hipStream_t st) {
+static int launch_gen(const KArgs& a, double* gws, hipStream_t st) {
     const size_t per = gen_ws_doubles(a.c.N);
     if (2 * a.c.N <= 64 * GEN_RMAX_SMALL)
         hipLaunchKernelGGL(solve_gen_kernel<GEN_RMAX_SMALL>, dim3(a.B), dim3(GEN_NT), 0, st, a, gws, per);
@@ -271,10 +253,6 @@ static int launch_long(const KArgs& a, double* lws, hipStream_t st) {
 int launch_split_step(const KArgs& a, double* sws, hipStream_t st, bool inlin);
 int launch_split_closed(const KArgs& a, double* sws, hipStream_t st);
 int launch_split_fused(const KArgs& a, double* sws, hipStream_t st);
-template <bool CLOSED>
-static int launch_split(const KArgs& a, double* sws, hipStream_t st) {
-    return CLOSED ? launch_split_closed(a, sws, st) : launch_split_step(a, sws, st, false);
-}
 
 // fused run queue order: the heaviest 10 % of the instances (by the previous launch's mean ADMM
 // iterations) one step ahead of the level front (mpc_solve.h; measured +1.9 % at the driver's 20-step
@@ -310,24 +288,21 @@ static int g_lead_steps = TGMPC_LEAD_STEPS, g_lead_permille = TGMPC_LEAD_PERMILL
 static int g_run_ahead = TGMPC_RUN_AHEAD;   // traj_debug_run_ahead
 // horizons up to which TRAJ_MAX_N < N runs the row-split kernel (mpc_split.h) instead of the long-horizon one
 // (traj_debug_split_max_n: 0 sends every N > TRAJ_MAX_N to the long-horizon kernel; the two agree to the step bars)
-static int g_split_max_n = TRAJ_MAX_N_SPLIT;
+static std::atomic<int> g_split_max_n{TRAJ_MAX_N_SPLIT};
 // horizons from which the step and the closed loop (fused and per step) run the row-split kernel: default
 // TRAJ_SPLIT_MIN_N = 21, so that 20 < N <= TRAJ_MAX_N_SPLIT all run it -- at config 3 (N = 40, mixed references) it is
 // 1.09-1.10 M steps/s against the capacity-80 kernel's 1.02 M (its iteration-cap chains at 0.76 instead of 1.16 us per
 // ADMM iteration), within +-3 % of it on spline references at N = 24 / 32 / 40 (profiles/r06_split_probe*.json);
 // traj_debug_split_min_n(TRAJ_MAX_N + 1) sends 20 < N <= TRAJ_MAX_N back to the capacity-80 kernel
-static int g_split_min_n = TRAJ_SPLIT_MIN_N;
-static bool split_route(const traj_mpc_config* c) {
-    return !state_bounds_active(c) && c->N >= g_split_min_n && c->N <= g_split_max_n;
-}
-// the row-split kernel's P scratch inside the workspace (after the base part): every horizon it can run, whatever the
-// routing, so that traj_mpc_workspace_bytes does not depend on a debug switch
-static size_t split_bytes(int B, int N) {
-    return (N >= 21 && N <= TRAJ_MAX_N_SPLIT) ? ((size_t)B * split_ws_doubles(N) + 2) * sizeof(double) : 0;
-}
-// traj_debug_step_linearize: the step's linearization inside the solve launch.  An atomic: a test that flips it may run
-// beside other callers of the library; each traj_mpc_step_batch reads it once.
+static std::atomic<int> g_split_min_n{TRAJ_SPLIT_MIN_N};
+// traj_debug_step_linearize: the step's linearization inside the solve launch.
 static std::atomic<int> g_step_inlin{1};
+// The three routing switches are atomics: a test that flips one may run beside other callers of the library.  Each
+// entry point reads them once (here) and routes the whole call by that snapshot (mpc_route.h).
+static Switches switches() {
+    return Switches{g_split_min_n.load(std::memory_order_relaxed), g_split_max_n.load(std::memory_order_relaxed),
+                    g_step_inlin.load(std::memory_order_relaxed)};
+}
 
 // per-kernel timing of traj_closed_loop_step (traj_debug_kernel_timing): 5 events per step bracket
 // rollout | jac | order | solve on the launch stream
@@ -335,6 +310,11 @@ static std::vector<hipEvent_t> g_ev;
 static int g_ev_used = 0;
 static inline void stamp(int k, hipStream_t st) {
     if ((size_t)(5 * g_ev_used + k) < g_ev.size()) (void)hipEventRecord(g_ev[5 * g_ev_used + k], st);
+}
+// the step's last stamp: the next step records into the next five events
+static inline void stamp_last(hipStream_t st) {
+    stamp(4, st);
+    if ((size_t)(5 * g_ev_used + 4) < g_ev.size()) ++g_ev_used;
 }
 
 static inline unsigned nblk(int B, int bs) { return (unsigned)((B + bs - 1) / bs); }
@@ -384,13 +364,13 @@ int traj_debug_run_ahead(int levels) {
 
 int traj_debug_split_min_n(int n_min) {
     if (n_min < 21 || n_min > TRAJ_MAX_N + 1) return TRAJ_E_ARG;
-    g_split_min_n = n_min;
+    g_split_min_n.store(n_min, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
 int traj_debug_split_max_n(int n_max) {
     if (n_max < 0 || n_max > TRAJ_MAX_N_SPLIT) return TRAJ_E_ARG;
-    g_split_max_n = n_max;
+    g_split_max_n.store(n_max, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
@@ -531,35 +511,20 @@ int traj_lateral_error_batch(int B, const double* X, const double* Y, const doub
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
 }
 
-static size_t ws_base_bytes(int B, int N);
-
-// lin: the step (linearization in the library, `ws` holds its hand-off + the state-bound scratch after
-// it); !lin: the QP half (Ad / Bd / g given, `ws` is only the state-bound scratch, may be NULL without
-// state bounds)
+// lin: the step (linearization in the library, `ws` holds its hand-off + the solver's scratch after it); !lin: the QP
+// half (Ad / Bd / g given, `ws` is only the solver's scratch, may be NULL where the route needs none)
 static int mpc_common(const traj_vehicle_params* p, const traj_mpc_config* c, int B, const double* x0,
                       const double* u_prev, const double* path_ref, const double* vref, const double* Ad,
                       const double* Bd, const double* g, double* u_cmd, int* status, double* objective,
                       double* X_opt, double* U_opt, int* iters, int* polished, void* ws, size_t ws_bytes,
                       void* stream, bool lin) {
-    if (!p || B < 0) return TRAJ_E_ARG;
-    int e = check_cfg(c, true);
-    if (e) return e;
+    if (!p) return TRAJ_E_ARG;
+    const Route r = route(c, B, lin ? Entry::Step : Entry::Qp, switches());
+    if (r.err) return r.err;
     if (B == 0) return TRAJ_OK;
     if (!x0 || !u_prev || !path_ref || !vref || !u_cmd || !status) return TRAJ_E_ARG;
     if (!lin && (!Ad || !Bd || !g)) return TRAJ_E_ARG;
-    // which solver (include/trajmpc.h tiers): the general one (state bounds, or N > TRAJ_MAX_N_LONG), the long-horizon
-    // one (TRAJ_MAX_N_SPLIT < N <= TRAJ_MAX_N_LONG), the row-split one (split_route; the QP entry point up to TRAJ_MAX_N
-    // keeps the capacity-80 kernel, which needs no scratch), or the register-resident ones.  Scratch: the step's
-    // workspace holds the row-split kernel's (traj_mpc_workspace_bytes); the others' follows it (+ sb bytes), as does
-    // the QP entry point's whole scratch
-    const bool use_split = split_route(c) && (lin || c->N > TRAJ_MAX_N);
-    const bool gen_long = state_bounds_active(c) || (c->N > TRAJ_MAX_N && !use_split);
-    const bool sb = gen_long || use_split;
-    const size_t base = lin ? ws_base_bytes(B, c->N) : 0;
-    const size_t need = lin ? base + (gen_long ? traj_mpc_sb_workspace_bytes(B, c->N)
-                                               : (use_split ? split_bytes(B, c->N) : 0))
-                            : (sb ? traj_mpc_sb_workspace_bytes(B, c->N) : 0);
-    if (need > 0 && (!ws || ws_bytes < need)) return TRAJ_E_ARG;
+    if (r.need > 0 && (!ws || ws_bytes < r.need)) return TRAJ_E_ARG;
     KArgs a;
     std::memset(&a, 0, sizeof(a));
     a.p = *p;
@@ -575,27 +540,19 @@ static int mpc_common(const traj_vehicle_params* p, const traj_mpc_config* c, in
     a.u_cmd = u_cmd; a.status = status; a.objective = objective; a.X_opt = X_opt; a.U_opt = U_opt;
     a.iters = iters; a.polished = polished;
     a.dbg = g_dbg;
-    // the step: one launch with the linearization in the workgroup (mode 4), or rollout_kernel + jac_kernel +
-    // the solve (traj_debug_step_linearize(0); the general solver always reads A/B/g from the workspace)
-    // (the row-split kernel likewise when it runs the step; the QP entry point and the other scratch solvers read A/B/g
-    // from the workspace)
-    const int inlin = g_step_inlin.load(std::memory_order_relaxed);
-    const bool split_inlin = use_split && lin && inlin;
-    if (lin && ((sb && !split_inlin) || !inlin)) launch_linearize(a, (hipStream_t)stream, false);
-    if (sb) {
-        double* const sws = (double*)((char*)ws + base);
-        if (use_split) return launch_split_step(a, sws, (hipStream_t)stream, split_inlin) ? TRAJ_E_LAUNCH : TRAJ_OK;
-        if (!state_bounds_active(c) && c->N <= TRAJ_MAX_N_LONG) return launch_long<false>(a, sws, (hipStream_t)stream);
-        return launch_general(a, sws, (hipStream_t)stream);
+    // the step: one launch with the linearization in the workgroup (the register-resident kernels' mode 4, the
+    // row-split kernel's INLIN instance), or rollout_kernel + jac_kernel before the solve (traj_debug_step_linearize(0);
+    // the long-horizon and general solvers always read A/B/g from the workspace, as the QP entry point's solvers do)
+    hipStream_t st = (hipStream_t)stream;
+    if (lin && !r.inlin) launch_linearize(a, st, false);
+    double* const sws = (double*)((char*)ws + r.scratch_off);
+    switch (r.tier) {
+        case Tier::Split: return launch_split_step(a, sws, st, r.inlin) ? TRAJ_E_LAUNCH : TRAJ_OK;
+        case Tier::Long: return launch_long<false>(a, sws, st);
+        case Tier::General: return launch_gen(a, sws, st);
+        case Tier::Reg: break;
     }
-    return launch_mpc(a, (hipStream_t)stream, lin ? (inlin ? 4 : 0) : 1);
-}
-
-// A/B/g hand-off (54 N doubles), rollout record (12 N), warm-start record (4), closed-loop order
-// (1 int), fused-run step queue (counter, error flag, completed and claimed steps per instance); a multiple of 8
-static size_t ws_base_bytes(int B, int N) {
-    return ((size_t)B * (size_t)N * 66 + (size_t)B * 4) * sizeof(double) +
-           ((((size_t)B * 3 + 2) * sizeof(int) + 7) & ~(size_t)7);
+    return launch_mpc(a, st, lin ? (r.inlin ? 4 : 0) : 1);
 }
 
 size_t traj_mpc_workspace_bytes(int B, int N) {
@@ -605,8 +562,17 @@ size_t traj_mpc_workspace_bytes(int B, int N) {
 
 size_t traj_mpc_sb_workspace_bytes(int B, int N) {
     if (B < 0 || N < 1 || N > TRAJ_MAX_N_GENERAL) return 0;
-    return (size_t)B * gen_ws_doubles(N) * sizeof(double);
+    return sb_bytes(B, N);
 }
+
+// what an entry point requires of `workspace_bytes`: the route's need, 0 for a configuration it refuses
+static size_t need_bytes(const traj_mpc_config* c, int B, Entry e) {
+    const Route r = route(c, B, e, switches());
+    return r.err ? 0 : r.need;
+}
+size_t traj_mpc_step_workspace_bytes(const traj_mpc_config* c, int B) { return need_bytes(c, B, Entry::Step); }
+size_t traj_mpc_qp_workspace_bytes(const traj_mpc_config* c, int B) { return need_bytes(c, B, Entry::Qp); }
+size_t traj_closed_loop_workspace_bytes(const traj_mpc_config* c, int B) { return need_bytes(c, B, Entry::ClosedStep); }
 
 int traj_mpc_step_batch(const traj_vehicle_params* p, const traj_mpc_config* c, int B, const double* x0,
                         const double* u_prev, const double* path_ref, const double* vref, double* u_cmd,
@@ -640,42 +606,21 @@ int traj_ref_window_batch(const traj_paths* paths, int B, int N, double Ts, cons
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
 }
 
-// The closed loop's horizons: N <= TRAJ_MAX_N on the register-resident kernels (fused or per step), TRAJ_MAX_N < N <=
-// TRAJ_MAX_N_LONG on the long-horizon kernel, one step per launch sequence (rollout_kernel + jac_kernel + the closed
-// solve_long_kernel).  The long tier needs the step's scratch beside the workspace, as the step entry point does:
-// traj_mpc_workspace_bytes + traj_mpc_sb_workspace_bytes.  With state bounds (mpc_6stati.py:208-213; main.py passes
-// none), or past TRAJ_MAX_N_LONG up to TRAJ_MAX_N_GENERAL, one step per launch sequence on the general solver
-// (closed_step_sb below).
-// (past TRAJ_MAX_N_LONG, or with state bounds: the general solver, closed_step_sb)
-static bool closed_general(const traj_mpc_config* c) { return state_bounds_active(c) || c->N > TRAJ_MAX_N_LONG; }
-static int check_cfg_closed(const traj_mpc_config* c) {
-    if (c && (c->N > TRAJ_MAX_N || split_route(c) || state_bounds_active(c))) return check_cfg(c, true);
-    return check_cfg(c);
-}
-// state bounds: the general solver's scratch after the workspace's base part (as the step's), then the step's window
-// [B, N+1, 3], u_cmd [B, 2] and a status row [B] (int)
-static size_t closed_sb_extra_off(int B, int N) { return ws_base_bytes(B, N) + traj_mpc_sb_workspace_bytes(B, N); }
-static size_t closed_sb_bytes(int B, int N) {
-    const size_t e = closed_sb_extra_off(B, N) + ((size_t)B * (3 * (size_t)(N + 1) + 2) + ((size_t)B + 1) / 2) * sizeof(double);
-    const size_t w = traj_mpc_workspace_bytes(B, N);
-    return e > w ? e : w;
-}
-static size_t closed_ws_bytes(const traj_mpc_config* c, int B) {
-    const int N = c->N;   // (the row-split kernel's scratch is in traj_mpc_workspace_bytes; the long-horizon one's follows)
-    if (closed_general(c)) return closed_sb_bytes(B, N);
-    return traj_mpc_workspace_bytes(B, N) + ((N > TRAJ_MAX_N && !split_route(c)) ? traj_mpc_sb_workspace_bytes(B, N) : 0);
-}
-// one long-horizon closed-loop step on a's state (a.t = the step, a.status / a.iters = this step's [B] rows)
-static int closed_step_long(const KArgs& a, void* ws, hipStream_t st) {
+// The closed loop by tier (mpc_route.h): the register-resident and row-split kernels fused (traj_closed_loop_run) or
+// per step; the long-horizon kernel and the general solver one step per launch sequence (closed_step_long /
+// closed_step_sb below), their scratch after the workspace's base part as the step entry point's.
+
+// one closed-loop step on the row-split or the long-horizon kernel (r.tier), on a's state (a.t = the step, a.status /
+// a.iters = this step's [B] rows): rollout_kernel + jac_kernel + the closed solve
+static int closed_step_long(const KArgs& a, const Route& r, void* ws, hipStream_t st) {
     stamp(0, st);
     launch_linearize(a, st, true);
     stamp(1, st);
     stamp(2, st);
     stamp(3, st);
-    double* const sws = (double*)((char*)ws + ws_base_bytes(a.B, a.c.N));
-    const int e = split_route(&a.c) ? launch_split<true>(a, sws, st) : launch_long<true>(a, sws, st);
-    stamp(4, st);
-    if ((size_t)(5 * g_ev_used + 4) < g_ev.size()) ++g_ev_used;
+    double* const sws = (double*)((char*)ws + r.scratch_off);
+    const int e = r.tier == Tier::Split ? launch_split_closed(a, sws, st) : launch_long<true>(a, sws, st);
+    stamp_last(st);
     return e;
 }
 
@@ -702,10 +647,11 @@ __global__ void closed_sb_plant_kernel(const KArgs a, const double* u_cmd) {
         a.hist_u[((size_t)b * a.hist_T + a.t) * 2 + 1] = u[1];
     }
 }
-static int closed_step_sb(const KArgs& a0, void* ws, hipStream_t st) {
+// (after the general solver's scratch in the workspace: the step's window [B, N+1, 3], u_cmd [B, 2], a status row [B])
+static int closed_step_sb(const KArgs& a0, const Route& r, void* ws, hipStream_t st) {
     const int B = a0.B, N = a0.c.N;
-    double* const sws = (double*)((char*)ws + ws_base_bytes(B, N));
-    double* const pr = (double*)((char*)ws + closed_sb_extra_off(B, N));
+    double* const sws = (double*)((char*)ws + r.scratch_off);
+    double* const pr = (double*)((char*)ws + r.scratch_off + r.scratch_bytes);
     double* const uc = pr + (size_t)B * 3 * (N + 1);
     int* const sbuf = (int*)(uc + (size_t)B * 2);
     stamp(0, st);
@@ -724,30 +670,17 @@ static int closed_step_sb(const KArgs& a0, void* ws, hipStream_t st) {
     stamp(1, st);
     stamp(2, st);
     stamp(3, st);
-    int e = launch_general(a, sws, st);
+    int e = launch_gen(a, sws, st);
     if (e) return e;
     hipLaunchKernelGGL(closed_sb_plant_kernel, dim3(nblk(B, 64)), dim3(64), 0, st, a0, (const double*)uc);
-    stamp(4, st);
-    if ((size_t)(5 * g_ev_used + 4) < g_ev.size()) ++g_ev_used;
+    stamp_last(st);
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
 }
 
-size_t traj_closed_loop_workspace_bytes(const traj_mpc_config* c, int B) {
-    if (!c || B < 0 || check_cfg_closed(c)) return 0;
-    return closed_ws_bytes(c, B);
-}
-
-int traj_closed_loop_step(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
-                          double* x, double* u_prev, const double* vref, int t, int hist_T, double* hist_x,
-                          double* hist_u, int* status, int* iters, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-    if (!p || B < 0 || !paths_ok(paths)) return TRAJ_E_ARG;
-    int e = check_cfg_closed(c);
-    if (e) return e;
-    if (B == 0) return TRAJ_OK;
-    if (!x || !u_prev || !vref) return TRAJ_E_ARG;
-    if (!workspace || workspace_bytes < closed_ws_bytes(c, B)) return TRAJ_E_ARG;
-    if ((hist_x || hist_u) && (t < 0 || t >= hist_T)) return TRAJ_E_ARG;
+// the closed-loop entry points' kernel arguments: the loop's state, the paths, the history and the carved workspace
+static KArgs closed_args(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                         double* x, double* u_prev, const double* vref, int t, int hist_T, double* hist_x,
+                         double* hist_u, int* status, int* iters, void* workspace) {
     KArgs a;
     std::memset(&a, 0, sizeof(a));
     a.p = *p;
@@ -765,9 +698,28 @@ int traj_closed_loop_step(const traj_vehicle_params* p, const traj_mpc_config* c
     a.iters = iters;
     a.dbg = g_dbg;
     carve_workspace(a, workspace, B, c->N);
+    return a;
+}
+
+int traj_closed_loop_step(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                          double* x, double* u_prev, const double* vref, int t, int hist_T, double* hist_x,
+                          double* hist_u, int* status, int* iters, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    if (!p || B < 0 || !paths_ok(paths)) return TRAJ_E_ARG;
+    const Route r = route(c, B, Entry::ClosedStep, switches());
+    if (r.err) return r.err;
+    if (B == 0) return TRAJ_OK;
+    if (!x || !u_prev || !vref) return TRAJ_E_ARG;
+    if (!workspace || workspace_bytes < r.need) return TRAJ_E_ARG;
+    if ((hist_x || hist_u) && (t < 0 || t >= hist_T)) return TRAJ_E_ARG;
+    KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, t, hist_T, hist_x, hist_u, status, iters, workspace);
     hipStream_t st = (hipStream_t)stream;
-    if (closed_general(c)) return closed_step_sb(a, workspace, st);
-    if (c->N > TRAJ_MAX_N || split_route(c)) return closed_step_long(a, workspace, st);
+    switch (r.tier) {
+        case Tier::General: return closed_step_sb(a, r, workspace, st);
+        case Tier::Split:
+        case Tier::Long: return closed_step_long(a, r, workspace, st);
+        case Tier::Reg: break;
+    }
     const int nr = (B + 63) / 64, nj = (B * c->N + 63) / 64;
     stamp(0, st);
     hipLaunchKernelGGL(rollout_kernel<true>, dim3(nr), dim3(64), 0, st, a);
@@ -781,9 +733,8 @@ int traj_closed_loop_step(const traj_vehicle_params* p, const traj_mpc_config* c
         a.perm = perm;
     }
     stamp(3, st);
-    e = launch_mpc(a, st, 2);
-    stamp(4, st);
-    if ((size_t)(5 * g_ev_used + 4) < g_ev.size()) ++g_ev_used;
+    const int e = launch_mpc(a, st, 2);
+    stamp_last(st);
     return e;
 }
 
@@ -792,28 +743,13 @@ int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c,
                          double* hist_x, double* hist_u, int* status, int* iters, void* workspace,
                          size_t workspace_bytes, void* stream) {
     if (!p || B < 0 || steps < 0 || !paths_ok(paths)) return TRAJ_E_ARG;
-    int e = check_cfg_closed(c);
-    if (e) return e;
+    const Route r = route(c, B, Entry::ClosedRun, switches());
+    if (r.err) return r.err;
     if (B == 0 || steps == 0) return TRAJ_OK;
     if (!x || !u_prev || !vref || t0 < 0) return TRAJ_E_ARG;
-    if (!workspace || workspace_bytes < closed_ws_bytes(c, B)) return TRAJ_E_ARG;
+    if (!workspace || workspace_bytes < r.need) return TRAJ_E_ARG;
     if ((hist_x || hist_u) && t0 + steps > hist_T) return TRAJ_E_ARG;
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.p = *p;
-    a.c = *c;
-    a.B = B;
-    a.vref = vref;
-    a.path = PathArgs{paths->kmax, paths->kind, paths->pc, paths->nk, paths->xk, paths->coef};
-    a.x_state = x;
-    a.u_state = u_prev;
-    a.t = t0;
-    a.hist_T = hist_T;
-    a.hist_x = hist_x;
-    a.hist_u = hist_u;
-    a.status = status;
-    a.iters = iters;
-    a.dbg = g_dbg;
+    KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, t0, hist_T, hist_x, hist_u, status, iters, workspace);
     a.nsteps = steps;
     a.fused_grid = g_fused_grid;
     // kernel instance: capacity 40, 2 waves per SIMD (3 from TRAJ_FUSED_W3_MIN_STEPS steps when that is set); capacity
@@ -825,24 +761,23 @@ int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c,
     a.wps = g_fused_waves ? g_fused_waves : (2 * c->N > 40 ? 1 : ((w3_min > 0 && steps >= w3_min) ? 3 : 2));
     a.spin_limit = g_spin_limit;
     a.dbg_items = g_dbg_items;
-    carve_workspace(a, workspace, B, c->N);
     hipStream_t st = (hipStream_t)stream;
     // step queue: [0] next work item, [1] error flag, [2 + b] steps of instance b completed, [2 + B + b] claimed
     a.queue = (int*)(a.wsWarm + (size_t)B * 4) + B;
     if (hipMemsetAsync(a.queue, 0, ((size_t)B * 2 + 2) * sizeof(int), st) != hipSuccess) return TRAJ_E_LAUNCH;
     a.run_ahead = g_run_ahead;
-    if (closed_general(c) || (c->N > TRAJ_MAX_N && !split_route(c))) {
-        // past the row-split capacity, or with state bounds: the steps as step launch sequences, in order on the
+    if (!r.fused) {
+        // the long-horizon kernel or the general solver: the steps as step launch sequences, in order on the
         // stream (the same results as that many traj_closed_loop_step calls; the queue above stays clear, so
         // traj_closed_loop_check reports TRAJ_OK)
-        const bool sb = closed_general(c);
         for (int s = 0; s < steps; ++s) {
             KArgs as = a;
             as.t = t0 + s;
             as.status = status ? status + (size_t)s * B : nullptr;
             as.iters = iters ? iters + (size_t)s * B : nullptr;
             as.nsteps = 0;
-            e = sb ? closed_step_sb(as, workspace, st) : closed_step_long(as, workspace, st);
+            const int e = r.tier == Tier::General ? closed_step_sb(as, r, workspace, st)
+                                                  : closed_step_long(as, r, workspace, st);
             if (e) return e;
         }
         return TRAJ_OK;
@@ -876,10 +811,9 @@ int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c,
     }
     stamp(3, st);
     // the row-split kernel's fused instance (the same queue protocol), or the register-resident one
-    e = split_route(c) ? launch_split_fused(a, (double*)((char*)workspace + ws_base_bytes(B, c->N)), st)
-                       : launch_mpc(a, st, 3);
-    stamp(4, st);
-    if ((size_t)(5 * g_ev_used + 4) < g_ev.size()) ++g_ev_used;
+    const int e = r.tier == Tier::Split ? launch_split_fused(a, (double*)((char*)workspace + r.scratch_off), st)
+                                        : launch_mpc(a, st, 3);
+    stamp_last(st);
     return e;
 }
 

@@ -289,8 +289,7 @@ def mpc_step(
     io.send()
     # the step entry point on the staged buffers directly (batch.mpc_step_batch's launch for B = 1, without its
     # per-call tensor views and conversions)
-    sb = int(_b._lib.lib().traj_mpc_sb_workspace_bytes(1, N)) if _b._general(cfg) else 0
-    ws = _b.workspace(1, N, dev, sb, role="step")
+    ws = _b.sized_workspace(_b._lib.lib().traj_mpc_step_workspace_bytes(C.byref(cfg), 1), dev, role="step")
     try:
         _b._lib.check(_b._lib.lib().traj_mpc_step_batch(C.byref(pst), C.byref(cfg), 1, *io.step_ptrs(N),
                                                         C.c_void_p(ws.data_ptr()), ws.numel() * 8,
