@@ -282,6 +282,47 @@ int traj_dataset_csv_device_format(int which, int B, int T, double Ts, const dou
 /* Synchronizes `stream` and returns TRAJ_E_LAUNCH if a write pass set *err, TRAJ_OK otherwise. */
 int traj_dataset_csv_device_check(const int* err, void* stream);
 
+/* ---- the files' text parsed on the device (csrc/dataset_parse.hip; dataset.read_csv_device) ----
+ * The inverse of the section above, with its conventions: DEVICE pointers (except the two _host functions'), `stream` a
+ * hipStream_t, asynchronous, no allocation, 64-bit byte and row counts.  `text` is a file's body (everything after the
+ * header line), nbytes long; no byte at or past nbytes is read.  The result is traj_dataset_read_csv's [rows, ncols]
+ * block bit for bit (traj_dataset_read_csv stays the default reader and the check).
+ *
+ * traj_dataset_parse_f64_host / _batch: the parser alone (csrc/parse_f64.h: Eisel-Lemire on at most 19 significant
+ * digits) on n fields, field i being text[off[i] .. off[i] + len[i]): status[i] = 0 and out[i] written, or status[i] = 1
+ * (declined: the grammar or the digit count is the host's business) and out[i] left as it was. */
+#define TRAJ_CSV_PARSE_CHUNK 4096   /* bytes per count of the line index (a multiple of 1024) */
+int traj_dataset_parse_f64_host(const char* text, const long long* off, const int* len, long long n, double* out,
+                                int* status);
+int traj_dataset_parse_f64_batch(const char* text, const long long* off, const int* len, long long n, double* out,
+                                 int* status, void* stream);
+/* Line index.  chunks = traj_dataset_csv_parse_chunks(nbytes) = ceil(nbytes / TRAJ_CSV_PARSE_CHUNK) (host, no launch;
+ * TRAJ_E_ARG if nbytes is negative or too large).  Count pass: counts[c] = the '\n's of chunk c.  The caller scans
+ * them (chunk_off = exclusive scan, 64-bit); rows = their sum, plus one if the text does not end in '\n' (a last line
+ * without '\n' is a row, a trailing '\n' starts no row): what traj_dataset_csv_rows returns for the file.  Starts pass:
+ * starts[r] = byte offset of row r's first byte; nothing is stored at or past starts + rows. */
+long long traj_dataset_csv_parse_chunks(long long nbytes);
+int traj_dataset_csv_parse_count(const char* text, long long nbytes, long long* counts /*[chunks]*/, void* stream);
+int traj_dataset_csv_parse_starts(const char* text, long long nbytes, const long long* chunk_off /*[chunks]*/,
+                                  long long* starts /*[rows]*/, long long rows, void* stream);
+/* Parse pass: out[r, c] = field c of row r, c < ncols (further fields are ignored; ',' separates, '\n', '\r' or the
+ * text's end closes a row), one row per thread.  *err (a device int the caller zeroes) gets bit 0 if a row has too few
+ * fields and bit 1 if starts does not describe rows inside the text (such rows are skipped).  A field the parser
+ * declines is NaN in out, adds one to *fb_count (the caller zeroes it) and, while the count is below cap, is recorded
+ * in fb_rec as (row, column, byte offset, length) for traj_dataset_csv_token_host. */
+int traj_dataset_csv_parse_rows(const char* text, long long nbytes, const long long* starts, long long rows, int ncols,
+                                double* out /*[rows,ncols]*/, int* err, unsigned long long* fb_count,
+                                long long* fb_rec /*[cap,4]*/, long long cap, void* stream);
+/* The loader's gather, cast and transpose in one pass: out[i, k, t] = (float)src[rowidx[i * T_steps + t], cols[k]] for
+ * i < n, k < ncols, t < T_steps, src being [rows, src_cols] float64.  The cast rounds to nearest even and keeps float32
+ * subnormals, on the bits.  An index outside src sets bit 1 of *err and stores nothing. */
+int traj_dataset_csv_gather_f32(const double* src, long long rows, int src_cols, const long long* rowidx /*[n,T_steps]*/,
+                                long long n, int T_steps, const int* cols /*[ncols]*/, int ncols,
+                                float* out /*[n,ncols,T_steps]*/, int* err, void* stream);
+/* Host: the reader's own token code (std::from_chars, then strtod past the double range, then the nan / inf
+ * spellings) on n non-empty fields of HOST text; TRAJ_E_ARG if one of them is no number (the others are still set). */
+int traj_dataset_csv_token_host(const char* text, const long long* off, const int* len, long long n, double* out);
+
 /* Data rows (header excluded) and columns of a CSV file; negative TRAJ_E_* on error. */
 long long traj_dataset_csv_rows(const char* path, int* ncols);
 /* All fields of the data rows as float64, row-major [rows, ncols] into out (e.g. pinned host memory);

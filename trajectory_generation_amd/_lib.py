@@ -23,6 +23,8 @@ MAX_N_SPLIT = 64      # the row-split kernel for SPLIT_MIN_N <= N <= MAX_N_SPLIT
 SPLIT_MIN_N = 21      # TRAJ_SPLIT_MIN_N
 MAX_N_LONG = 256      # step / QP entry points on the long-horizon kernel without state bounds (TRAJ_MAX_N_LONG)
 MAX_N_GENERAL = 1024  # step / QP entry points on the general solver (TRAJ_MAX_N_GENERAL)
+CSV_PARSE_CHUNK = 4096  # bytes per count of the device CSV parser's line index (TRAJ_CSV_PARSE_CHUNK)
+PARSE_OK, PARSE_FALLBACK = 0, 1   # csrc/parse_f64.h
 
 STATUS_STRINGS = {
     0: "optimal",
@@ -167,6 +169,16 @@ _SIGS = {
     "traj_dataset_csv_device_format": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _V, _V, _V, _V, C.c_longlong,
                                                  C.c_longlong, _V, _V, C.c_longlong, _V, C.c_longlong, _V, _V]),
     "traj_dataset_csv_device_check": (C.c_int, [_V, _V]),
+    "traj_dataset_parse_f64_host": (C.c_int, [_V, _V, _V, C.c_longlong, _V, _V]),
+    "traj_dataset_parse_f64_batch": (C.c_int, [_V, _V, _V, C.c_longlong, _V, _V, _V]),
+    "traj_dataset_csv_parse_chunks": (C.c_longlong, [C.c_longlong]),
+    "traj_dataset_csv_parse_count": (C.c_int, [_V, C.c_longlong, _V, _V]),
+    "traj_dataset_csv_parse_starts": (C.c_int, [_V, C.c_longlong, _V, _V, C.c_longlong, _V]),
+    "traj_dataset_csv_parse_rows": (C.c_int, [_V, C.c_longlong, _V, C.c_longlong, C.c_int, _V, _V, _V, _V, C.c_longlong,
+                                              _V]),
+    "traj_dataset_csv_gather_f32": (C.c_int, [_V, C.c_longlong, C.c_int, _V, C.c_longlong, C.c_int, _V, C.c_int, _V, _V,
+                                              _V]),
+    "traj_dataset_csv_token_host": (C.c_int, [_V, _V, _V, C.c_longlong, _V]),
     "traj_dataset_csv_rows": (C.c_longlong, [C.c_char_p, _V]),
     "traj_dataset_read_csv": (C.c_int, [C.c_char_p, C.c_longlong, C.c_int, _V, C.c_int]),
     "traj_debug_kernel_times": (C.c_int, [_V, _V]),

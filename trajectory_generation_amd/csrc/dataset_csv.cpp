@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/trajmpc.h"
+#include "csv_token.h"
 
 namespace {
 
@@ -228,21 +229,8 @@ int traj_dataset_read_csv(const char* path, long long rows, int ncols, double* o
                 while (*e != ',' && *e != '\n' && *e != '\r') ++e;
                 if (e == s) {
                     o[c] = NAN;
-                } else {
-                    auto res = std::from_chars(s, e, o[c]);
-                    if (res.ec == std::errc::result_out_of_range && res.ptr == e) {
-                        // a literal past the double range: the value Python's float() / pandas give it (+-inf, or a
-                        // signed zero / the nearest subnormal), from strtod on the token
-                        std::string tok(s, e);
-                        o[c] = std::strtod(tok.c_str(), nullptr);
-                    } else if (res.ec != std::errc() || res.ptr != e) {
-                        // "nan" / "inf" spellings pandas may write
-                        std::string tok(s, e);
-                        if (tok == "nan" || tok == "NaN") o[c] = NAN;
-                        else if (tok == "inf") o[c] = INFINITY;
-                        else if (tok == "-inf") o[c] = -INFINITY;
-                        else err.store(1, std::memory_order_relaxed);
-                    }
+                } else if (!tgcsv::csv_token_f64(s, e, &o[c])) {
+                    err.store(1, std::memory_order_relaxed);
                 }
                 if (c + 1 < ncols) {
                     if (*e != ',') { err.store(1, std::memory_order_relaxed); break; }
@@ -252,6 +240,18 @@ int traj_dataset_read_csv(const char* path, long long rows, int ncols, double* o
         }
     });
     return err.load() ? TRAJ_E_ARG : TRAJ_OK;
+}
+
+int traj_dataset_csv_token_host(const char* text, const long long* off, const int* len, long long n, double* out) {
+    if (n < 0 || (n > 0 && (!text || !off || !len || !out))) return TRAJ_E_ARG;
+    int rc = TRAJ_OK;
+    for (long long i = 0; i < n; ++i) {
+        if (off[i] < 0 || len[i] < 0) return TRAJ_E_ARG;
+        const char* s = text + off[i];
+        if (len[i] == 0) out[i] = NAN;
+        else if (!tgcsv::csv_token_f64(s, s + len[i], &out[i])) rc = TRAJ_E_ARG;
+    }
+    return rc;
 }
 
 }  // extern "C"

@@ -625,15 +625,309 @@ def read_csv_native(path, nthreads=None, pin=False):
     return names, buf
 
 
+DEVICE_CSV_READ_SLAB_BYTES = 64 << 20   # read_csv_device: pinned staging, two slabs of this size
+DEVICE_CSV_FALLBACK_CAP = 4096          # read_csv_device: declined fields settled one by one; more: the host reader
+
+
+def _tokens_block(tokens):
+    """A list of bytes as (one uint8 array, int64 offsets, int32 lengths)."""
+    ln = np.array([len(t) for t in tokens], dtype=np.int32)
+    off = np.zeros(len(tokens), dtype=np.int64)
+    if len(tokens):
+        off[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+    text = np.frombuffer(b"".join(tokens) + b"\0", dtype=np.uint8).copy()   # never empty; the last byte is no field's
+    return text, off, ln
+
+
+def parse_f64_host(tokens, fill=0.0):
+    """csrc/parse_f64.h on the CPU (traj_dataset_parse_f64_host) on a list of bytes: (float64 array, int32 statuses);
+    a declined token (status _lib.PARSE_FALLBACK) leaves `fill`."""
+    import ctypes as C
+    from . import _lib
+    text, off, ln = _tokens_block(tokens)
+    out = np.full(len(tokens), fill, dtype=np.float64)
+    st = np.full(len(tokens), -7, dtype=np.int32)
+    p = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    _lib.check(_lib.lib().traj_dataset_parse_f64_host(p(text), p(off), p(ln), len(tokens), p(out), p(st)),
+               "traj_dataset_parse_f64_host")
+    return out, st
+
+
+def parse_f64_batch(tokens, fill=0.0, device=None):
+    """The same header on the GPU (traj_dataset_parse_f64_batch), one field per thread: a list of bytes ->
+    (float64 CUDA tensor, int32 statuses); a declined token leaves `fill`."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    dev = torch.device("cuda" if device is None else device)
+    text, off, ln = _tokens_block(tokens)
+    n = len(tokens)
+    with torch.cuda.device(dev):
+        td, od, ld = (torch.from_numpy(a).to(dev) for a in (text, off, ln))
+        out = torch.full((n,), fill, dtype=torch.float64, device=dev)
+        st = torch.full((n,), -7, dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        _lib.check(_lib.lib().traj_dataset_parse_f64_batch(p(td), p(od), p(ld), n, p(out), p(st),
+                                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "traj_dataset_parse_f64_batch")
+        torch.cuda.current_stream().synchronize()
+    return out, st
+
+
+def csv_tokens_host(tokens):
+    """The host reader's own token code (traj_dataset_csv_token_host: std::from_chars, strtod past the double range,
+    the nan / inf spellings) on a list of non-empty bytes: (float64 array, True if every token is a number)."""
+    import ctypes as C
+    from . import _lib
+    text, off, ln = _tokens_block(tokens)
+    out = np.zeros(len(tokens), dtype=np.float64)
+    p = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    rc = _lib.lib().traj_dataset_csv_token_host(p(text), p(off), p(ln), len(tokens), p(out))
+    return out, rc == _lib.TRAJ_OK
+
+
+def csv_parse_index(text, nbytes, events=None):
+    """The line index of a file body on the device (uint8 CUDA tensor `text`, its first nbytes bytes), on the current
+    stream: (rows, starts) with starts the int64 CUDA tensor of every row's first byte.  events: a dict that receives
+    (start, end) CUDA event pairs named count, scan and starts."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    dev = text.device
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+
+    def timed(name, fn):
+        if events is None:
+            return fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        r = fn()
+        b.record()
+        events[name] = (a, b)
+        return r
+
+    chunks = int(L.traj_dataset_csv_parse_chunks(int(nbytes)))
+    if chunks < 0:
+        raise ValueError(f"csv_parse_index: {nbytes} bytes")
+    if chunks == 0:
+        return 0, torch.empty(0, dtype=torch.int64, device=dev)
+    counts = torch.empty(chunks, dtype=torch.int64, device=dev)
+    timed("count", lambda: _lib.check(L.traj_dataset_csv_parse_count(p(text), int(nbytes), p(counts), st),
+                                      "traj_dataset_csv_parse_count"))
+    cum = timed("scan", lambda: torch.cumsum(counts, 0))
+    chunk_off = cum - counts
+    # a last line without its newline is a row; a trailing newline starts none
+    rows = int(cum[-1]) + (0 if int(text[nbytes - 1]) == 0x0A else 1)
+    starts = torch.empty(rows, dtype=torch.int64, device=dev)
+    timed("starts", lambda: _lib.check(L.traj_dataset_csv_parse_starts(p(text), int(nbytes), p(chunk_off), p(starts), rows,
+                                                                       st), "traj_dataset_csv_parse_starts"))
+    return rows, starts
+
+
+def csv_parse_rows(text, nbytes, starts, rows, ncols, out, err, fb_count, fb_rec):
+    """traj_dataset_csv_parse_rows on the current stream: the rows at `starts` of the body `text` (its first nbytes
+    bytes) into the float64 CUDA tensor out [rows, ncols]; err (int32), fb_count (int64) and fb_rec ([cap, 4] int64)
+    are the device error word, the declined fields' counter and their records."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    _lib.check(_lib.lib().traj_dataset_csv_parse_rows(p(text), int(nbytes), p(starts), int(rows), int(ncols), p(out),
+                                                      p(err), p(fb_count), p(fb_rec), int(fb_rec.shape[0]),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "traj_dataset_csv_parse_rows")
+
+
+def csv_gather_f32(src, rowidx, n, T_steps, cols):
+    """traj_dataset_csv_gather_f32 on the current stream: src [rows, C] float64 (CUDA), rowidx [n * T_steps] int64 row
+    numbers, cols a list of column numbers -> [n, len(cols), T_steps] float32, cast with round to nearest even."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    dev = src.device
+    out = torch.empty((n, len(cols), T_steps), dtype=torch.float32, device=dev)
+    cd = torch.tensor(list(cols), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    _lib.check(_lib.lib().traj_dataset_csv_gather_f32(p(src), src.shape[0], src.shape[1], p(rowidx), int(n), int(T_steps),
+                                                      p(cd), len(cols), p(out), p(err),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "traj_dataset_csv_gather_f32")
+    if int(err[0]):
+        raise RuntimeError("traj_dataset_csv_gather_f32: a row or column index outside the parsed block")
+    return out
+
+
+def _upload_body(f, nbytes, dev, slab_bytes, tm):
+    """nbytes bytes of the open file f into a new uint8 CUDA tensor through two pinned slabs: a thread reads slab k + 1
+    from the file while slab k is copied up."""
+    import threading
+    import queue
+    import time
+    import torch
+    text = torch.empty(nbytes + 16, dtype=torch.uint8, device=dev)     # the tail is never read
+    slab = max(1, min(int(slab_bytes), nbytes))
+    hbuf = [torch.empty(slab, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    hnp = [h.numpy() for h in hbuf]
+    free = [threading.Semaphore(1), threading.Semaphore(1)]
+    filled = queue.Queue()
+    failed = []
+
+    def reader():
+        try:
+            done, k = 0, 0
+            while done < nbytes:
+                i = k & 1
+                free[i].acquire()
+                t0 = time.perf_counter()
+                want = min(slab, nbytes - done)
+                mv, got = memoryview(hnp[i])[:want], 0
+                while got < want:
+                    r = f.readinto(mv[got:])
+                    if not r:
+                        raise ValueError("read_csv_device: the file shrank while it was read")
+                    got += r
+                tm["file_read_s"] += time.perf_counter() - t0
+                filled.put((i, done, want))
+                done += want
+                k += 1
+        except BaseException as e:   # noqa: BLE001  (reported by the caller's thread)
+            failed.append(e)
+        filled.put(None)
+
+    th = threading.Thread(target=reader, daemon=True)
+    th.start()
+    copy_stream = torch.cuda.Stream(device=dev)
+    copies, prev = [], None
+    while True:
+        item = filled.get()
+        if item is None:
+            break
+        i, o, nb = item
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(copy_stream):
+            c0.record()
+            text[o:o + nb].copy_(hbuf[i][:nb], non_blocking=True)
+            c1.record()
+        copies.append((c0, c1))
+        if prev is not None:           # the copy before this one has left its slab: the reader may fill it again
+            prev[1].synchronize()
+            free[prev[0]].release()
+        prev = (i, c1)
+    th.join()
+    copy_stream.synchronize()
+    if failed:
+        raise failed[0]
+    torch.cuda.current_stream().wait_stream(copy_stream)
+    tm["h2d_s"] += sum(a.elapsed_time(b) for a, b in copies) * 1e-3
+    return text
+
+
+def read_csv_device(path, device=None, timings=None, fallback_cap=None, slab_bytes=DEVICE_CSV_READ_SLAB_BYTES):
+    """read_csv_native with the text parsed on the GPU (csrc/dataset_parse.hip): (names, [rows, C] float64 CUDA tensor),
+    the tensor equal to read_csv_native's bit for bit.  Opt-in; read_csv_native stays the check of this one.
+
+    The header line is parsed on the host; the body goes through two pinned slabs of slab_bytes to the device whole
+    (read and copy overlapped), where a count pass, a 64-bit scan and a starts pass index its lines and a parse pass
+    takes one row per thread (csrc/parse_f64.h: Eisel-Lemire on at most 19 significant digits).  A field the device
+    declines (more digits, a '+' sign, any other spelling) is recorded; the host reader's own token code
+    (traj_dataset_csv_token_host) settles up to fallback_cap (default DEVICE_CSV_FALLBACK_CAP) of them from the file's
+    bytes and the values are scattered into the tensor; with more, the whole file goes through read_csv_native and is
+    copied up.  So the two readers agree by construction on everything the device declines.  Raises what read_csv_native
+    raises: RuntimeError for a field that is no number or a row with too few fields.
+    timings: a dict that receives file_read_s, h2d_s, kernels_s, kernel_ms (count, scan, starts, parse), fallback_s,
+    fallback_fields, rows, bytes and total_s."""
+    import os
+    import time
+    import torch
+    from . import _lib
+    t_start = time.perf_counter()
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError("read_csv_device parses on a CUDA device (read_csv_native reads into host memory)")
+    cap = DEVICE_CSV_FALLBACK_CAP if fallback_cap is None else int(fallback_cap)
+    tm = {"file_read_s": 0.0, "h2d_s": 0.0, "kernels_s": 0.0, "kernel_ms": {}, "fallback_s": 0.0, "fallback_fields": 0,
+          "rows": 0, "bytes": 0}
+
+    def finish(names, t):
+        tm["total_s"] = time.perf_counter() - t_start
+        if timings is not None:
+            timings.update(tm)
+        return names, t
+
+    with open(path, "rb") as f:
+        header = f.readline()
+    names = header.decode().strip().split(",")
+    if header.count(b",") + 1 != len(names):
+        raise ValueError(f"{path}: not a dataset CSV ({header.count(b',') + 1} columns)")
+    ncols = len(names)
+    with torch.cuda.device(dev):
+        with open(path, "rb", buffering=0) as f:
+            nbytes = os.fstat(f.fileno()).st_size - len(header)
+            tm["bytes"] = nbytes + len(header)
+            if nbytes <= 0 or not header.endswith(b"\n"):
+                return finish(names, torch.empty((0, ncols), dtype=torch.float64, device=dev))
+            f.seek(len(header))
+            text = _upload_body(f, nbytes, dev, slab_bytes, tm)
+        ev = {}
+        rows, starts = csv_parse_index(text, nbytes, ev)
+        out = torch.empty((rows, ncols), dtype=torch.float64, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        fb_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        fb_rec = torch.zeros((max(cap, 1), 4), dtype=torch.int64, device=dev)
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        k0.record()
+        csv_parse_rows(text, nbytes, starts, rows, ncols, out, err, fb_count, fb_rec[:cap])
+        k1.record()
+        ev["parse"] = (k0, k1)
+        n_fb, flag = int(fb_count[0]), int(err[0])      # waits for the stream
+        tm["kernel_ms"] = {k: a.elapsed_time(b) for k, (a, b) in ev.items()}
+        tm["kernels_s"] = sum(tm["kernel_ms"].values()) * 1e-3
+        tm["fallback_fields"], tm["rows"] = n_fb, rows
+        if flag & 2:
+            raise RuntimeError("traj_dataset_csv_parse_rows: the line index does not describe the text")
+        if flag & 1:
+            _lib.check(_lib.TRAJ_E_ARG, "read_csv_device (a row with too few fields)")
+        if n_fb > cap:
+            del text, out, starts
+            t0 = time.perf_counter()
+            names, buf = read_csv_native(path, pin=True)
+            out = buf.to(dev)
+            tm["fallback_s"] = time.perf_counter() - t0
+            return finish(names, out)
+        if n_fb:
+            t0 = time.perf_counter()
+            rec = fb_rec[:n_fb].cpu().numpy()
+            tokens = []
+            with open(path, "rb") as f:
+                for _, _, off, ln in rec:
+                    f.seek(len(header) + int(off))
+                    tokens.append(f.read(int(ln)))
+            vals, ok = csv_tokens_host(tokens)
+            if not ok:
+                _lib.check(_lib.TRAJ_E_ARG, "read_csv_device (a field that is no number)")
+            flat = torch.from_numpy(rec[:, 0] * ncols + rec[:, 1]).to(dev)
+            out.view(-1)[flat] = torch.from_numpy(vals).to(dev)
+            tm["fallback_s"] = time.perf_counter() - t0
+    return finish(names, out)
+
+
 def load_vehicle_dataset(noisy_csv_path, clean_csv_path, T_steps=600, train_split=0.7, val_split=0.15, seed=42,
-                         device=None, native=False):
+                         device=None, native=False, device_csv=False):
     """KalmanNet/data_loader.py:5-109 (load_vehicle_dataset), vectorized: the first T_steps rows of every
     trajectory (ids 0..n-1), y = noisy [X, Y, vx, vy, omega], u = [d, delta], x = clean
     [X, Y, phi, vx, vy, omega] as float32 [n, C, T]; trajectories shuffled by default_rng(seed) and split
     70 / 15 / 15.  Returns ((y, u, x) train, val, test) torch tensors (on ``device`` if given), or None
-    when a file or a trajectory is missing, as the reference does."""
+    when a file or a trajectory is missing, as the reference does.
+    native: opt-in -- the library's host parser instead of pandas (_load_native), the same tensors.
+    device_csv: opt-in -- the files' text is parsed and grouped on the GPU (_load_device: read_csv_device, device ops,
+      one gather / cast / transpose kernel per block); the same tensors, on ``device`` (default: the current GPU)."""
     import pandas as pd
     import torch
+    if device_csv:
+        return _load_device(noisy_csv_path, clean_csv_path, T_steps, train_split, val_split, seed, device)
     if native:
         return _load_native(noisy_csv_path, clean_csv_path, T_steps, train_split, val_split, seed, device)
     try:
@@ -713,3 +1007,59 @@ def _load_native(noisy_csv_path, clean_csv_path, T_steps, train_split, val_split
         return t.to(device) if device is not None else t
 
     return tuple(tuple(dev(p) for p in part) for part in zip(cut(y), cut(u), cut(x)))
+
+
+def _load_device(noisy_csv_path, clean_csv_path, T_steps, train_split, val_split, seed, device, timings=None):
+    """load_vehicle_dataset with the text parsed on the GPU: read_csv_device per file, _load_native's grouping as
+    device ops (n = the noisy file's distinct ids; rows with id < n, stably sorted by id; every id needs T_steps rows;
+    the first T_steps of each), then traj_dataset_csv_gather_f32 with the shuffled trajectory order
+    (default_rng(seed).shuffle, drawn on the host) folded into its row index.  An id column with anything but
+    non-negative integers hands the whole call to _load_native.  timings: a dict that receives each file's
+    read_csv_device timings (noisy, clean), grouping_s (the device ops and the gather kernels, wall time) and gather_ms
+    (the gather kernels alone, device events)."""
+    import os
+    import time
+    import torch
+    if not (os.path.exists(noisy_csv_path) and os.path.exists(clean_csv_path)):
+        return None
+    dev = torch.device("cuda" if device is None else device)
+    tm = {"grouping_s": 0.0, "gather_ms": 0.0}
+    blocks = []
+    n = perm = None
+    with torch.cuda.device(dev):
+        for key, path, cols in (("noisy", noisy_csv_path, (["X", "Y", "vx", "vy", "omega"], ["d", "delta"])),
+                                ("clean", clean_csv_path, (["X", "Y", "phi", "vx", "vy", "omega"],))):
+            tm[key] = {}
+            names, a = read_csv_device(path, device=dev, timings=tm[key])
+            t0 = time.perf_counter()
+            tf = a[:, names.index("trajectory_id")]
+            if not bool(((tf >= 0) & (tf < 2.0 ** 62) & (tf == tf.floor())).all()):
+                return _load_native(noisy_csv_path, clean_csv_path, T_steps, train_split, val_split, seed, dev)
+            tid = tf.to(torch.int64)
+            if n is None:
+                n = int(torch.unique(tid).numel())
+                idx = np.arange(n)
+                np.random.default_rng(seed).shuffle(idx)
+                perm = torch.from_numpy(idx).to(dev)
+            keep = torch.nonzero(tid < n).reshape(-1)
+            kept = tid[keep]
+            order = keep[torch.argsort(kept, stable=True)]
+            counts = torch.bincount(kept, minlength=n)
+            if counts.numel() != n or n == 0 or bool((counts < T_steps).any()):
+                return None
+            first = torch.cumsum(counts, 0) - counts
+            rowidx = order[(first[perm][:, None] + torch.arange(T_steps, device=dev)[None, :]).reshape(-1)].contiguous()
+            g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            g0.record()
+            for cl in cols:
+                blocks.append(csv_gather_f32(a, rowidx, n, T_steps, [names.index(c) for c in cl]))
+            g1.record()
+            torch.cuda.current_stream().synchronize()
+            tm["grouping_s"] += time.perf_counter() - t0
+            tm["gather_ms"] += g0.elapsed_time(g1)
+    y, u, x = blocks
+    n_tr, n_va = int(n * train_split), int(n * val_split)
+    cut = lambda t: (t[:n_tr], t[n_tr:n_tr + n_va], t[n_tr + n_va:])   # noqa: E731
+    if timings is not None:
+        timings.update(tm)
+    return tuple(tuple(part) for part in zip(cut(y), cut(u), cut(x)))
