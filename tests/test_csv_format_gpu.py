@@ -175,3 +175,50 @@ def test_generators_write_the_same_files_either_way(gen, tmp):
         out[dev] = (open(prefix + "_clean.csv", "rb").read(), open(prefix + "_noisy.csv", "rb").read())
     assert out[False][0].count(b"\n") == 1 + 4 * 7
     assert_same(out[True], out[False])
+
+
+def test_drop_failed_writes_the_same_files_three_ways(tmp):
+    """_write_with_sidecar(drop_failed=True) on device tensors through the device writer, on device tensors through
+    the host writer and on numpy arrays: trajectories 2 and 4 of 6 have a failed step, the other four are re-indexed
+    0..3 and keep the noise of their generation ids 10, 11, 13, 15.  One warning each, the same bytes in all three
+    files."""
+    B, T = 6, 4
+    rng = np.random.default_rng(64)
+    X, U = rng.standard_normal((B, T + 1, 6)), rng.uniform(-1, 1, (B, T, 2))
+    st = np.zeros((T, B), dtype=np.int32)
+    st[0, 1], st[1, 2], st[3, 4] = 1, 6, 2
+    ids = np.arange(10, 16)
+    Xd, Ud, std = torch.from_numpy(X).cuda(), torch.from_numpy(U).cuda(), torch.from_numpy(st).cuda()
+    out = {}
+    for name, args, dev in (("dev", (Xd, Ud, std), True), ("host", (Xd, Ud, std), False), ("np", (X, U, st), False)):
+        prefix = os.path.join(tmp, f"drop_{name}")
+        with pytest.warns(UserWarning, match="left out 2 of 6"):
+            D._write_with_sidecar(prefix, *args, ids, TS, True, dev)
+        out[name] = tuple(open(f"{prefix}_{part}.csv", "rb").read() for part in ("clean", "noisy", "status"))
+    assert_same(out["dev"], out["np"])
+    assert_same(out["host"], out["np"])
+    status = [ln.split(b",") for ln in out["np"][2].splitlines()[1:]]
+    assert [int(r[0]) for r in status] == [0, 1, 2, 3] and [int(r[1]) for r in status] == [10, 11, 13, 15]
+    for text in out["np"][:2]:
+        rows = text.splitlines()[1:]
+        assert [int(r.rsplit(b",", 1)[1]) for r in rows] == [i for i in range(4) for _ in range(T + 1)]
+    # the noise is that of the generation ids, not of the written ids
+    want = os.path.join(tmp, "drop_want")
+    keep = [0, 1, 3, 5]
+    D.write_csv(want, X[keep], U[keep], np.arange(4), TS, noise_ids=ids[keep])
+    assert_same(out["np"][:2], (open(want + "_clean.csv", "rb").read(), open(want + "_noisy.csv", "rb").read()))
+
+
+@pytest.mark.parametrize("dev", [False, True])
+@pytest.mark.parametrize("gen", ["generate_open_loop", "generate_piecewise"])
+def test_open_loop_shard_equals_the_single_file(gen, dev, tmp):
+    """shards=True without a process group: rank 0's shard is the whole dataset, so its files are the shards=False
+    files byte for byte; no status sidecar either way."""
+    fn = getattr(D, gen)
+    one, sh = os.path.join(tmp, f"{gen}_one_{int(dev)}"), os.path.join(tmp, f"{gen}_sh_{int(dev)}")
+    fn(4, 6, out_prefix=one, device_csv=dev)
+    r = fn(4, 6, out_prefix=sh, shards=True, device_csv=dev)
+    assert len(r) == 2 and tuple(r[0].shape) == (4, 7, 6) and tuple(r[1].shape) == (4, 6, 2)
+    assert_same([open(f"{sh}_rank0_{part}.csv", "rb").read() for part in ("clean", "noisy")],
+                [open(f"{one}_{part}.csv", "rb").read() for part in ("clean", "noisy")])
+    assert not os.path.exists(f"{sh}_rank0_status.csv") and not os.path.exists(f"{one}_status.csv")

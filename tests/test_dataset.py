@@ -136,6 +136,64 @@ def test_generate_two_ranks_per_rank_shards_gloo(tmp_path):
         assert shards[0][1:] + shards[1][1:] == one[1:]
 
 
+def _fake_generate_steps(B, T, Ts, seed=0, id_offset=0):
+    """CPU stand-in for generation_type1 / generation_type2.generate_steps: histories that encode id and step."""
+    ids = np.arange(id_offset, id_offset + B)
+    X = torch.tensor(ids[:, None, None] + 0.01 * np.arange(T + 1)[None, :, None] + np.zeros((1, 1, 6)))
+    U = torch.tensor(-ids[:, None, None] + np.zeros((1, T, 2)))
+    return {"X": X, "U": U, "ids": ids}
+
+
+def _xu_worker(rank, world, port, q, out_prefix, shards):
+    from trajectory_generation_amd.dataset.generate import _generate_xu
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    r = _generate_xu(_fake_generate_steps, 4, 6, 0.01, 42, out_prefix, dist, shards, False)
+    q.put((rank, None if r is None else tuple(t.numpy() for t in r)))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_open_loop_tail_two_ranks_gloo(tmp_path):
+    """The open-loop generators' tail (dataset.generate._generate_xu) at world size 2 (gloo).  Gathered: the
+    histories reach rank 0 only, in global id order, and rank 0 writes ids 0..7.  shards=True: every rank keeps
+    its share and the two shards' bodies in rank order are the gathered file's body byte for byte.  No status
+    sidecar in either mode."""
+    import glob
+    ctx = mp.get_context("spawn")
+    got = {}
+    for shards, name in ((False, "one"), (True, "sh")):
+        q = ctx.Queue()
+        port = _free_port()
+        procs = [ctx.Process(target=_xu_worker, args=(r, 2, port, q, str(tmp_path / name), shards)) for r in range(2)]
+        for p in procs:
+            p.start()
+        got[shards] = dict(q.get(timeout=120) for _ in range(2))
+        for p in procs:
+            p.join(timeout=120)
+            assert p.exitcode == 0
+    assert got[False][1] is None                       # rank 1 receives nothing
+    gX, gU = got[False][0]
+    assert gX.shape == (8, 7, 6) and gU.shape == (8, 6, 2)
+    np.testing.assert_array_equal(gX[:, 1, 0], np.arange(8) + 0.01)   # rank order == global id order
+    np.testing.assert_array_equal(gU[:, 0, 0], -np.arange(8))
+    for r in range(2):                                  # shards: this rank's share, nothing gathered
+        sX, sU = got[True][r]
+        np.testing.assert_array_equal(sX, gX[4 * r:4 * r + 4])
+        np.testing.assert_array_equal(sU, gU[4 * r:4 * r + 4])
+    for part in ("clean", "noisy"):
+        one = (tmp_path / f"one_{part}.csv").read_bytes().split(b"\n", 1)
+        ids = [int(ln.rsplit(b",", 1)[1]) for ln in one[1].splitlines()]
+        assert ids == [i for i in range(8) for _ in range(7)]
+        sh = [(tmp_path / f"sh_rank{r}_{part}.csv").read_bytes().split(b"\n", 1) for r in range(2)]
+        assert sh[0][0] == sh[1][0] == one[0]
+        assert sh[0][1] + sh[1][1] == one[1]
+    assert not glob.glob(str(tmp_path / "*_status.csv"))
+    assert sorted(os.listdir(tmp_path)) == sorted(
+        [f"one_{p}.csv" for p in ("clean", "noisy")] + [f"sh_rank{r}_{p}.csv" for r in range(2) for p in ("clean", "noisy")])
+
+
 def _status_closed_loop(w, T, cfg):
     """Stand-in with chosen statuses: trajectory 2 fails at step 1 (solver error), 4 at step 3 (iteration
     limit, status 2); everything else optimal / optimal_inaccurate."""

@@ -1,4 +1,4 @@
-"""RCCL on the box (diagnostics): the collectives bench.py / dataset.py issue -- barrier, MAX all-reduce of a
+"""RCCL on the box (diagnostics): the collectives bench.py / dataset/generate.py issue -- barrier, MAX all-reduce of a
 float64 scalar, and the dataset gather of one [B, T+1, 9] float64 block per rank (dist.gather, called directly so
 that it runs at world size 1 too, where dataset.gather_to_root short-circuits).  Launch with torch.distributed.run;
 rank 0 prints one JSON line."""

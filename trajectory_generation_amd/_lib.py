@@ -5,6 +5,7 @@ There is no CPU fallback: if the library or a GPU is missing, every entry point 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -274,6 +275,35 @@ def check(rc: int, what: str):
         if rc == TRAJ_E_UNSUPPORTED:
             raise NotImplementedError(f"{what}: {msg}")
         raise RuntimeError(f"{what} failed: {msg} ({rc})")
+
+
+def ptr(a):
+    """The address of a tensor's or a numpy array's first element as c_void_p; None stays None (a null pointer)."""
+    if a is None:
+        return None
+    return C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+
+def stream(dev=None):
+    """The current stream of `dev` (default: the current device) as c_void_p."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+@contextlib.contextmanager
+def event_pair(into=None, key=None):
+    """``with event_pair(into, key) as (a, b): ...`` records the timing event a on entry and b on exit, both on the
+    stream current at that point.  The pair is appended to `into` if that is a list, stored as into[key] if it is a
+    dict, and only handed to the caller if it is None."""
+    import torch
+    pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    pair[0].record()
+    yield pair
+    pair[1].record()
+    if isinstance(into, dict):
+        into[key] = pair
+    elif into is not None:
+        into.append(pair)
 
 
 def default_params() -> VehicleParams:

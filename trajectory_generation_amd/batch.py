@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 from ._lib import FsmRules, GenConfig, MpcConfig, Paths, VehicleParams
 
 REFERENCE_PARAMS = {
@@ -81,14 +82,6 @@ def _dev(x, shape=None, device=None) -> torch.Tensor:
     if shape is not None:
         t = t.reshape(shape)
     return t.contiguous()
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---------------------------------------------------------------- physics

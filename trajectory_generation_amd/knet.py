@@ -37,20 +37,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 from .batch import REFERENCE_PARAMS, params_struct, require_gpu
 
 Params = dict(REFERENCE_PARAMS)
 
 LIMIT_KEYS = ("x_min", "x_max", "y_min", "y_max", "phi_min", "phi_max", "vx_min", "vx_max", "vy_min", "vy_max",
               "omega_min", "omega_max")
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def limits_struct(params: dict) -> _lib.KnetLimits:

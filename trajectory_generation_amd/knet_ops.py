@@ -33,6 +33,7 @@ import torch
 from torch.library import custom_op, register_fake
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 from .batch import REFERENCE_PARAMS
 
 NET_PTRS = ("fc5_w", "fc5_b", "gru_q_wih", "gru_q_bih", "gru_q_whh", "gru_q_bhh", "gru_sigma_wih", "gru_sigma_bih",
@@ -82,14 +83,6 @@ def step_dims(model) -> List[int]:
 
 
 # ---------------------------------------------------------------- helpers
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
 
 def _params_struct(vals: Sequence[float]) -> _lib.VehicleParams:
     s = _lib.VehicleParams()

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 from .batch import params_struct, require_gpu
 from .knet import KalmanNetNN, KNetSequenceRunner, limits_struct
 
@@ -35,14 +36,6 @@ T_START_EVAL = 50     # :33
 INIT_MODE = "noisy_gt"   # :40
 INIT_NOISE_STD = 0.2     # :41
 INIT_SEED = 0            # :42
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def init_states(x_gt, x_mean, x_std, mode=INIT_MODE, noise_std=INIT_NOISE_STD, seed=INIT_SEED):
