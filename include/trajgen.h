@@ -23,6 +23,8 @@
 #ifndef TRAJGEN_H
 #define TRAJGEN_H
 
+#include <stdint.h>
+
 #include "trajmpc.h"
 
 #ifdef __cplusplus
@@ -85,7 +87,8 @@ int traj_gen_debug_store_form(int form);
  * are the same arithmetic on the same inputs, so one integration per lane serves both.  The random stream
  * is numpy's Generator(PCG64), reproduced in the kernel (csrc/gen_rng.h); the caller supplies each
  * trajectory's generator state, np.random.PCG64(seed + i).state, as four uint64
- * (state >> 64, state & (2^64 - 1), inc >> 64, inc & (2^64 - 1)). */
+ * (state >> 64, state & (2^64 - 1), inc >> 64, inc & (2^64 - 1)) -- taken from numpy, or computed from the seed by
+ * traj_gen_seed_pcg64_host / _batch below. */
 
 /* The rules of generation_type2.py:22-30 that the controller reads, and the two mode distributions of
  * :109-112 as cumulative sums, cdf = p.cumsum() / p.cumsum()[-1] (what Generator.choice searches). */
@@ -155,6 +158,20 @@ int traj_gen_rng_draw_host(const unsigned long long* state /*[4]*/, int kind, lo
 int traj_gen_rng_draw_batch(int B, int n, int kind, const unsigned long long* states /*[B,4]*/,
                             void* out /*[B,n]*/, unsigned long long* states_out /*[B,4] or NULL*/,
                             void* stream);
+
+/* ---- np.random.PCG64(entropy).state from the entropy (csrc/seed_seq.h: numpy's SeedSequence.generate_state(4, uint64)
+ * and PCG64's seeding from those four words, in integer arithmetic: equal to numpy's or wrong) ----
+ * entropy [B,nwords]: per stream the entropy as numpy coerces an int or a sequence of ints -- uint32 words,
+ * little-endian, at least one word per int, a sequence's words concatenated (the caller's, i.e. Python's, job; numpy
+ * refuses a negative int and so must the caller).  Every stream of a call has nwords words, 1 <= nwords <= 8; zero
+ * words appended to a shorter entropy change nothing as long as nwords <= 4 (SeedSequence's pool size).
+ * states [B,4]: the layout of traj_gen_piecewise_batch's rng_state.
+ * _host: host pointers, synchronous.  _batch: device pointers, asynchronous on `stream`, one thread per stream.
+ * TRAJ_E_ARG: null pointer (when B > 0), B < 0, nwords outside 1 .. 8.  B == 0: TRAJ_OK, no launch. */
+int traj_gen_seed_pcg64_host(const uint32_t* entropy /*[B,nwords]*/, int B, int nwords,
+                             unsigned long long* states /*[B,4]*/);
+int traj_gen_seed_pcg64_batch(const uint32_t* entropy /*[B,nwords]*/, int B, int nwords,
+                              unsigned long long* states /*[B,4]*/, void* stream);
 
 #ifdef __cplusplus
 }

@@ -282,6 +282,38 @@ int traj_dataset_csv_device_format(int which, int B, int T, double Ts, const dou
 /* Synchronizes `stream` and returns TRAJ_E_LAUNCH if a write pass set *err, TRAJ_OK otherwise. */
 int traj_dataset_csv_device_check(const int* err, void* stream);
 
+/* ---- the noisy file's measurement noise drawn on the device (csrc/dataset_noise.hip; dataset.measurement_noise_device) ----
+ * noise[b, r, ch], [B,n_rows,6] as traj_dataset_write_csv and the two calls above read it, is what
+ *   rng = np.random.default_rng(seed_base + noise_ids[b]);  np.column_stack([rng.normal(0, sigma[ch], n_rows) for ch])
+ * gives (dataset.measurement_noise): the stream seeded through csrc/seed_seq.h, six channels of n_rows normals drawn
+ * one after the other through csrc/gen_rng.h, 0.0 + sigma[ch] * z stored.  seed_base + noise_ids[b] must not be
+ * negative.  sigma [6] is a HOST pointer, read before the call returns.  tie_margin >= 0: a comparison of the
+ * ziggurat against exp or log1p (the wedge test, the tail test) whose two sides are within that relative distance
+ * sets declined[b] = 1 (otherwise 0): the trajectory's stream may have parted from numpy's on a libm that is not the
+ * host's, and its block is the caller's to redraw on the host.
+ *
+ * traj_dataset_noise_host: HOST pointers, synchronous; the host libm is numpy's, so the block is numpy's whatever
+ * declined (may be NULL) reports.
+ * traj_dataset_noise_batch: DEVICE pointers, asynchronous on `stream`, one lane per trajectory.  Every accepted tail
+ * draw (|z| > 3.654...) adds one to *tail_count (a device counter the caller zeroes) and, while the count is below
+ * tail_capacity, is recorded in tail_rec as four 64-bit words: the element's index in noise, the bits of the two
+ * uniforms u1, u2 that went through log1p, and 1 for a negative draw.  The device's own value is stored too.
+ * traj_dataset_noise_tails_host (HOST pointers): per record the value the host libm gives, 0.0 + sigma[index % 6] * z,
+ * and accepted = 1 if the host's tail test accepts (u1, u2) as the device's did; the caller stores the values over the
+ * device's and redraws a trajectory whose record is not accepted.
+ * TRAJ_E_ARG: null pointer (data pointers only when B > 0 / n > 0; tail_rec only when tail_capacity > 0), B < 0,
+ * n_rows < 1, tie_margin negative or NaN, tail_capacity < 0, n < 0, and for _host a negative seed_base + noise_ids[b].
+ * B == 0: TRAJ_OK, no launch. */
+int traj_dataset_noise_host(int B, int n_rows, long long seed_base, const long long* noise_ids /*[B]*/,
+                            const double* sigma /*[6]*/, double tie_margin, double* noise /*[B,n_rows,6]*/,
+                            int* declined /*[B] or NULL*/);
+int traj_dataset_noise_batch(int B, int n_rows, long long seed_base, const long long* noise_ids /*[B]*/,
+                             const double* sigma /*[6], host*/, double tie_margin, double* noise /*[B,n_rows,6]*/,
+                             int* declined /*[B]*/, unsigned long long* tail_count,
+                             unsigned long long* tail_rec /*[tail_capacity,4]*/, long long tail_capacity, void* stream);
+int traj_dataset_noise_tails_host(long long n, const unsigned long long* tail_rec /*[n,4]*/,
+                                  const double* sigma /*[6]*/, double* value /*[n]*/, int* accepted /*[n]*/);
+
 /* ---- the files' text parsed on the device (csrc/dataset_parse.hip; dataset.read_csv_device) ----
  * The inverse of the section above, with its conventions: DEVICE pointers (except the two _host functions'), `stream` a
  * hipStream_t, asynchronous, no allocation, 64-bit byte and row counts.  `text` is a file's body (everything after the

@@ -1,6 +1,7 @@
-"""Host CSV writer against the device CSV path at the reference's dataset size -> profiles/csv_device_bench.json.
+"""Host CSV writer against the device CSV path at the reference's dataset size -> profiles/csv_device_bench.json
+(with --device-noise: the three writers -> profiles/csv_device_noise_bench.json).
 
-  python tools/csv_device_bench.py [--B 5000] [--T 1200] [--reps 3] [--out-dir DIR] [--json PATH]
+  python tools/csv_device_bench.py [--B 5000] [--T 1200] [--reps 3] [--out-dir DIR] [--json PATH] [--device-noise]
 
 One process, one type-2 dataset (generation_type2.generate_steps) left on the GPU.  After one warm-up of each, the two
 writers alternate `reps` times:
@@ -8,6 +9,11 @@ writers alternate `reps` times:
           (measurement_noise per trajectory), traj_dataset_write_csv in 16 threads (format + one file write per file);
   device  dataset.write_csv_device: the text formatted on the GPU in slabs, copied down through two pinned buffers and
           written, the noise drawn in a background thread meanwhile (also timed with 16 drawing threads).
+With --device-noise a third writer alternates with the two in the same process:
+  device_noise  write_csv_device(device_noise=True): the noise drawn on the GPU before the clean file starts
+          (measurement_noise_device), no drawing thread and no upload;
+the 16-thread variant and the /dev/null run are left out, the three files pairs are compared, and
+generation_type2.pcg64_states at B seeds is timed on the host and on the device.
 Per path: each stage and the wall time of the whole call (median, min, max over the repeats).  The host writer also
 runs once per repeat into /dev/null, which separates its formatting from its file write.  The last repeat's files are
 compared byte for byte (SHA-256).  Needs the GPU; there is no CPU fallback.
@@ -64,12 +70,78 @@ def host_path(D, _lib, prefix, X, U, ids, Ts, nthreads, to_null=False):
     return tm
 
 
-def device_path(D, prefix, X, U, ids, Ts, nthreads, slab_bytes):
+def device_path(D, prefix, X, U, ids, Ts, nthreads, slab_bytes, device_noise=False):
     import torch
     tm = {}
     torch.cuda.synchronize()
-    D.write_csv_device(prefix, X, U, ids, Ts, slab_bytes=slab_bytes, nthreads=nthreads, timings=tm)
+    D.write_csv_device(prefix, X, U, ids, Ts, slab_bytes=slab_bytes, nthreads=nthreads, timings=tm,
+                       **({"device_noise": True} if device_noise else {}))
     return tm
+
+
+def seed_bench(n, reps):
+    """generation_type2.pcg64_states at n seeds: numpy's SeedSequence on the host against traj_gen_seed_pcg64_batch
+    (wall time to the states being on the device in both cases; the kernel alone by device events)."""
+    import torch
+    from trajectory_generation_amd import _lib
+    from trajectory_generation_amd import generation_type2 as G2
+    seeds = [2025 + i for i in range(n)]
+    host, dev, kern = [], [], []
+    same = True
+    for _ in range(reps + 1):
+        t0 = time.perf_counter()
+        h = torch.from_numpy(G2.pcg64_states(seeds).view(np.int64)).cuda()
+        torch.cuda.synchronize()
+        host.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        d = G2.pcg64_states(seeds, device="cuda:0")
+        torch.cuda.synchronize()
+        dev.append(time.perf_counter() - t0)
+        same = same and bool(torch.equal(h, d))
+        ent = torch.from_numpy(G2.seed_entropy_words(seeds).view(np.int32)).cuda()
+        out = torch.empty((n, 4), dtype=torch.int64, device="cuda:0")
+        with _lib.event_pair() as ev:
+            _lib.check(_lib.lib().traj_gen_seed_pcg64_batch(_lib.ptr(ent), n, ent.shape[1], _lib.ptr(out),
+                                                            _lib.stream()), "traj_gen_seed_pcg64_batch")
+        torch.cuda.synchronize()
+        kern.append(ev[0].elapsed_time(ev[1]))
+    return {"seeds": n, "identical": same, "host_s": spread(host[1:]), "device_s": spread(dev[1:]),
+            "device_kernel_ms": spread(kern[1:])}
+
+
+def three_writers(a, D, _lib, X, U, ids, slab, tmp):
+    """--device-noise: host writer, device path (host draw: the parent's path) and device path with the device draw,
+    alternating in one process."""
+    import torch
+    pfx = {k: os.path.join(tmp, k) for k in ("host", "device", "device_noise")}
+    run = {"host": lambda: host_path(D, _lib, pfx["host"], X, U, ids, a.Ts, a.nthreads),
+           "device": lambda: device_path(D, pfx["device"], X, U, ids, a.Ts, a.noise_threads, slab),
+           "device_noise": lambda: device_path(D, pfx["device_noise"], X, U, ids, a.Ts, a.noise_threads, slab, True)}
+    for f in run.values():      # warm-up of each
+        f()
+    res = {k: [] for k in run}
+    for _ in range(a.reps):
+        for k, f in run.items():
+            res[k].append(f())
+    digests = {k: [sha(f"{p}_{kind}.csv") for kind in ("clean", "noisy")] for k, p in pfx.items()}
+    same = digests["host"] == digests["device"] == digests["device_noise"]
+    nbytes = sum(os.path.getsize(f"{pfx['host']}_{kind}.csv") for kind in ("clean", "noisy"))
+    for p in pfx.values():
+        for kind in ("clean", "noisy"):
+            os.remove(f"{p}_{kind}.csv")
+    fold = lambda runs: {k: spread([r[k] for r in runs]) for k in runs[0] if k not in ("bytes", "slabs")}   # noqa: E731
+    out = {"B": a.B, "T": a.T, "Ts": a.Ts, "reps": a.reps, "nthreads": a.nthreads,
+           "device": torch.cuda.get_device_name(0), "csv_bytes": nbytes, "files_identical": bool(same),
+           "host_writer": fold(res["host"]),
+           "device_path_host_noise": dict(fold(res["device"]), slab_bytes=slab, noise_threads=a.noise_threads),
+           "device_path_device_noise": dict(fold(res["device_noise"]), slab_bytes=slab)}
+    h, d = out["device_path_host_noise"], out["device_path_device_noise"]
+    out["host_noise_over_device_noise_total_at_median"] = h["total_s"]["median"] / d["total_s"]["median"]
+    out["device_noise_faster_at_median"] = bool(d["total_s"]["median"] < h["total_s"]["median"])
+    out["device_noise_faster_beyond_spread"] = bool(d["total_s"]["max"] < h["total_s"]["min"])
+    out["noise_draw_s_host_over_device_at_median"] = h["noise_draw_s"]["median"] / d["noise_draw_s"]["median"]
+    out["pcg64_states"] = seed_bench(a.B, a.reps)
+    return out, same
 
 
 def main():
@@ -82,8 +154,11 @@ def main():
     ap.add_argument("--noise-threads", type=int, default=1)
     ap.add_argument("--slab-bytes", type=int, default=None)
     ap.add_argument("--out-dir", default=None)
-    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "csv_device_bench.json"))
+    ap.add_argument("--device-noise", action="store_true")
+    ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    a.json = a.json or os.path.join(ROOT, "profiles", "csv_device_noise_bench.json" if a.device_noise
+                                    else "csv_device_bench.json")
     import torch
     from trajectory_generation_amd import _lib
     from trajectory_generation_amd import dataset as D
@@ -96,6 +171,15 @@ def main():
     torch.cuda.synchronize()
     tmp = a.out_dir or tempfile.mkdtemp(prefix="csvbench_")
     os.makedirs(tmp, exist_ok=True)
+    if a.device_noise:
+        out, same = three_writers(a, D, _lib, X, U, ids, slab, tmp)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out, indent=1))
+        if not same or not out["pcg64_states"]["identical"]:
+            raise SystemExit("the writers' files or the seeded states differ")
+        return
     hp, dp = os.path.join(tmp, "host"), os.path.join(tmp, "device")
     # warm-up of each (code objects, pinned allocations, page cache of the target files)
     host_path(D, _lib, hp, X, U, ids, a.Ts, a.nthreads)

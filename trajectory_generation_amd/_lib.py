@@ -26,6 +26,7 @@ MAX_N_LONG = 256      # step / QP entry points on the long-horizon kernel withou
 MAX_N_GENERAL = 1024  # step / QP entry points on the general solver (TRAJ_MAX_N_GENERAL)
 CSV_PARSE_CHUNK = 4096  # bytes per count of the device CSV parser's line index (TRAJ_CSV_PARSE_CHUNK)
 PARSE_OK, PARSE_FALLBACK = 0, 1   # csrc/parse_f64.h
+SEED_SEQ_MAX_WORDS = 8            # csrc/seed_seq.h: entropy words per stream the seeding entry points take
 
 STATUS_STRINGS = {
     0: "optimal",
@@ -170,6 +171,10 @@ _SIGS = {
     "traj_dataset_csv_device_format": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _V, _V, _V, _V, C.c_longlong,
                                                  C.c_longlong, _V, _V, C.c_longlong, _V, C.c_longlong, _V, _V]),
     "traj_dataset_csv_device_check": (C.c_int, [_V, _V]),
+    "traj_dataset_noise_host": (C.c_int, [C.c_int, C.c_int, C.c_longlong, _V, _V, C.c_double, _V, _V]),
+    "traj_dataset_noise_batch": (C.c_int, [C.c_int, C.c_int, C.c_longlong, _V, _V, C.c_double, _V, _V, _V, _V,
+                                           C.c_longlong, _V]),
+    "traj_dataset_noise_tails_host": (C.c_int, [C.c_longlong, _V, _V, _V, _V]),
     "traj_dataset_parse_f64_host": (C.c_int, [_V, _V, _V, C.c_longlong, _V, _V]),
     "traj_dataset_parse_f64_batch": (C.c_int, [_V, _V, _V, C.c_longlong, _V, _V, _V]),
     "traj_dataset_csv_parse_chunks": (C.c_longlong, [C.c_longlong]),
@@ -232,6 +237,8 @@ _SIGS = {
                                            C.c_int, _V, _V, _V, _V, _V, _V, _V]),
     "traj_gen_rng_draw_host": (C.c_int, [_V, C.c_int, C.c_longlong, _V, _V]),
     "traj_gen_rng_draw_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _V, _V, _V, _V]),
+    "traj_gen_seed_pcg64_host": (C.c_int, [_V, C.c_int, C.c_int, _V]),
+    "traj_gen_seed_pcg64_batch": (C.c_int, [_V, C.c_int, C.c_int, _V, _V]),
     "traj_closed_loop_step": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
                                         _V, _V, _V, C.c_int, C.c_int, _V, _V, _V, _V, _V, C.c_size_t, _V]),
     "traj_closed_loop_run": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,

@@ -204,14 +204,19 @@ def simulate_piecewise(x0, rng_state, T, Ts=0.01, rules=None, params=None, want_
     """B type-2 trajectories of T steps in one launch (traj_gen_piecewise_batch): the state-machine controller of
     generation_type2.py:95-157 on each trajectory's own numpy stream, and the Euler loop of :180-187, from x0 [B,6].
     rng_state [B,4] uint64: np.random.PCG64(seed + i).state as (state >> 64, state & M, inc >> 64, inc & M)
-    (generation_type2.pcg64_states).  Returns torch.cuda tensors X [B,T+1,6], U [B,T,2], mode [B,T] uint8 (codes of
+    (generation_type2.pcg64_states; or its int64 CUDA tensor of the same bits).  Returns torch.cuda tensors X [B,T+1,6], U [B,T,2], mode [B,T] uint8 (codes of
     _lib.FSM_MODES) and, with want_rng_state, rng_state [B,4] int64 (the bits of the uint64 words) after the last draw."""
     x0 = _dev(x0, (-1, 6))
     B, T = x0.shape[0], int(T)
-    st = np.ascontiguousarray(rng_state, dtype=np.uint64)
-    if st.shape != (B, 4):
-        raise ValueError(f"rng_state must be [B,4] uint64 with B = {B}, got {st.shape}")
-    st = torch.from_numpy(st.view(np.int64)).to(x0.device)
+    if torch.is_tensor(rng_state):      # already on the device (generation_type2.pcg64_states with a device)
+        if tuple(rng_state.shape) != (B, 4) or rng_state.dtype != torch.int64:
+            raise ValueError(f"rng_state must be [B,4] int64 (the uint64 words' bits) with B = {B}")
+        st = rng_state.to(x0.device).contiguous()
+    else:
+        st = np.ascontiguousarray(rng_state, dtype=np.uint64)
+        if st.shape != (B, 4):
+            raise ValueError(f"rng_state must be [B,4] uint64 with B = {B}, got {st.shape}")
+        st = torch.from_numpy(st.view(np.int64)).to(x0.device)
     X = torch.empty((B, T + 1, 6), dtype=torch.float64, device=x0.device)
     U = torch.empty((B, T, 2), dtype=torch.float64, device=x0.device)
     mode = torch.empty((B, T), dtype=torch.uint8, device=x0.device)

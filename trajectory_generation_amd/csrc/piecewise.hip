@@ -20,39 +20,11 @@
 #include "../../include/trajgen.h"
 #include "gen_model.h"
 #include "gen_rng.h"
+#include "gen_zig_lds.h"
 
 namespace tgmpc {
 
-// the tables twice: the host's copy (traj_gen_rng_draw_host) and the device's (the source of the LDS copy)
-#define GEN_ZIG_DECL static const
-#define GEN_ZIG_NAME(x) zig_host_##x
-#include "gen_zig_tables.h"
-#undef GEN_ZIG_DECL
-#undef GEN_ZIG_NAME
-#define GEN_ZIG_DECL static __device__ const
-#define GEN_ZIG_NAME(x) zig_dev_##x
-#include "gen_zig_tables.h"
-#undef GEN_ZIG_DECL
-#undef GEN_ZIG_NAME
-
 constexpr int PW_WAVE = 64;
-constexpr int ZIG_N = 256;
-
-struct ZigLds {
-    double wi[ZIG_N];
-    uint64_t ki[ZIG_N];
-    double fi[ZIG_N];
-};
-
-// every thread of the block takes part; ends with a barrier
-__device__ __forceinline__ void zig_load(ZigLds& t) {
-    for (int i = threadIdx.x; i < ZIG_N; i += blockDim.x) {
-        t.wi[i] = zig_dev_wi[i];
-        t.ki[i] = zig_dev_ki[i];
-        t.fi[i] = zig_dev_fi[i];
-    }
-    __syncthreads();
-}
 
 __host__ __device__ __forceinline__ void pcg_load(Pcg64& s, const unsigned long long* p) {
     s.hi = p[0]; s.lo = p[1]; s.inc_hi = p[2]; s.inc_lo = p[3];

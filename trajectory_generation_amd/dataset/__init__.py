@@ -30,5 +30,7 @@ from .generate import (_write_with_sidecar, _write_xu, gather_to_root, generate,
                        generate_piecewise, merge_datasets, pack_history, status_summary, unpack_history,
                        write_status_csv)
 from .loader import _load_device, _load_native, load_vehicle_dataset  # noqa: F401
+from .noise import (NOISE_TIE_MARGIN, measurement_noise_device, measurement_noise_host, noise_device_raw,  # noqa: F401
+                    noise_sigma, noise_tails_host)
 from .schema import (CLEAN_COLUMNS, FAILED_STATUS, HIST_CHANNELS, MEAS_NOISE_STD, NOISE_SEED_BASE,  # noqa: F401
                      NOISY_COLUMNS, frames, measurement_noise)

@@ -175,7 +175,7 @@ def _device_csv_file(path, which, X, U, noise, ids_d, Ts, half, dbuf, hbuf, tm):
 
 
 def write_csv_device(out_prefix, X, U, ids, Ts, noise_ids=None, slab_bytes=DEVICE_CSV_SLAB_BYTES, nthreads=None,
-                     timings=None):
+                     timings=None, device_noise=False):
     """write_csv for X [B,T+1,6], U [B,T,2] that are CUDA tensors: the same two files, byte for byte, with the text
     formatted on the GPU (csrc/dataset_fmt.hip: one file row per thread, a length pass, a 64-bit scan of the lengths,
     a write pass) so the host only copies bytes down and writes them.  Opt-in; write_csv(native=True) stays the
@@ -188,7 +188,12 @@ def write_csv_device(out_prefix, X, U, ids, Ts, noise_ids=None, slab_bytes=DEVIC
     formatted and written, then uploaded for the noisy file (x + noise is added on the device, one IEEE add as on the
     host).  nthreads: threads of that draw (default 1: seeding 5,000 generators is interpreter-bound, and 16 threads
     measured slower than one).  timings: a dict that receives noise_draw_s, h2d_s, kernel_ms and d2h_ms (device events, summed),
-    file_write_s, clean_file_s and noisy_file_s (wall time of each file's pipeline), bytes, slabs and total_s."""
+    file_write_s, clean_file_s and noisy_file_s (wall time of each file's pipeline), bytes, slabs and total_s.
+
+    device_noise: opt-in (default False: the host draw above) -- the noise is drawn on the GPU before the clean file
+    starts (measurement_noise_device: the same bits, csrc/dataset_noise.hip), so there is no drawing thread, no pinned
+    noise buffer and no upload.  timings then also gets noise_kernel_ms, noise_tails and noise_declined; noise_draw_s is
+    the wall time of the device draw with its host patch, and h2d_s is 0."""
     import threading
     import time
     import torch
@@ -208,6 +213,12 @@ def write_csv_device(out_prefix, X, U, ids, Ts, noise_ids=None, slab_bytes=DEVIC
     nt = int(nthreads or 1)
     tm = {"noise_draw_s": 0.0, "h2d_s": 0.0, "kernel_ms": 0.0, "d2h_ms": 0.0, "file_write_s": 0.0, "bytes": 0,
           "slabs": 0}
+    if device_noise:
+        _write_csv_device_noise(out_prefix, X, U, ids_h, nids, Ts, half, tm)
+        tm["total_s"] = time.perf_counter() - t_start
+        if timings is not None:
+            timings.update(tm)
+        return
     noise_h = torch.empty((B, n_rows, 6), dtype=torch.float64, pin_memory=B > 0)
     nh = noise_h.numpy()
     drawn = []
@@ -252,3 +263,27 @@ def write_csv_device(out_prefix, X, U, ids, Ts, noise_ids=None, slab_bytes=DEVIC
     tm["total_s"] = time.perf_counter() - t_start
     if timings is not None:
         timings.update(tm)
+
+
+def _write_csv_device_noise(out_prefix, X, U, ids_h, nids, Ts, half, tm):
+    """write_csv_device(device_noise=True) after its argument checks: the noise drawn on the device, then the two
+    files one after the other."""
+    import time
+    import torch
+    from .noise import measurement_noise_device
+    with torch.cuda.device(X.device):
+        t0 = time.perf_counter()
+        st = {}
+        noise_d = measurement_noise_device(nids, X.shape[1], X.device, stats=st)
+        torch.cuda.current_stream().synchronize()
+        tm["noise_draw_s"] = time.perf_counter() - t0
+        tm.update(noise_kernel_ms=st["kernel_ms"], noise_tails=st["tails"], noise_declined=st["declined"])
+        X = X.to(torch.float64).contiguous()
+        U = U.to(torch.float64).contiguous()
+        ids_d = torch.from_numpy(ids_h).to(X.device)
+        dbuf = [torch.empty(half, dtype=torch.uint8, device=X.device) for _ in range(2)]
+        hbuf = [torch.empty(half, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        for which, name, noise in ((0, "clean", None), (1, "noisy", noise_d)):
+            t0 = time.perf_counter()
+            _device_csv_file(f"{out_prefix}_{name}.csv", which, X, U, noise, ids_d, Ts, half, dbuf, hbuf, tm)
+            tm[f"{name}_file_s"] = time.perf_counter() - t0

@@ -100,7 +100,7 @@ def _run_rank(run, B, out_prefix, dist, shards, write):
 
 
 def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=None, polish_mode=0,
-             closed_loop=None, drop_failed=False, shards=False, device_csv=False):
+             closed_loop=None, drop_failed=False, shards=False, device_csv=False, device_noise=False):
     """Run the closed loop for this rank's B trajectories (ids rank * B .. rank * B + B - 1), gather the
     histories to rank 0 and (rank 0) write ``{out_prefix}_clean.csv`` / ``{out_prefix}_noisy.csv`` and the
     status sidecar ``{out_prefix}_status.csv`` (write_status_csv).
@@ -118,9 +118,12 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
     closed loop); tests inject a CPU stand-in to exercise the id offsets and the gather.
     device_csv: opt-in (default False: the host writer, write_csv) -- the CSVs' text is formatted on the GPU from the
       device tensors (write_csv_device, the same bytes).
+    device_noise: opt-in, with device_csv only (ValueError otherwise) -- the noisy file's measurement noise is drawn on
+      the GPU too (measurement_noise_device, the same bits).
     Returns (X [W B,T+1,6], U [W B,T,2], status [T,W B]) on rank 0 and None on the other ranks (shards:
     this rank's (X, U, status) everywhere)."""
     from ..workload import make_workload
+    _check_device_noise(device_csv, device_noise)
     cfg = None
     if closed_loop is None:
         from .. import batch as TB
@@ -134,34 +137,44 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
         return res["X"], res["U"], res["status"]
 
     return _run_rank(run, B, out_prefix, dist, shards, lambda prefix, X, U, st, ids: _write_with_sidecar(
-        prefix, X, U, st, ids, Ts, drop_failed, device_csv))
+        prefix, X, U, st, ids, Ts, drop_failed, device_csv, device_noise))
 
 
-def _generate_xu(generate_steps, B, T, Ts, seed, out_prefix, dist, shards, device_csv):
+def _check_device_noise(device_csv, device_noise):
+    if device_noise and not device_csv:
+        raise ValueError("device_noise=True draws the noise for write_csv_device: it needs device_csv=True")
+
+
+def _generate_xu(generate_steps, B, T, Ts, seed, out_prefix, dist, shards, device_csv, device_noise=False, **gen_kw):
     """generate_open_loop / generate_piecewise around their module's generate_steps: no step can fail, so the gather
-    carries no status and no sidecar is written."""
+    carries no status and no sidecar is written.  gen_kw: further keywords of generate_steps."""
+    _check_device_noise(device_csv, device_noise)
+
     def run(id_offset):
-        res = generate_steps(B, T, Ts, seed=seed, id_offset=id_offset)
+        res = generate_steps(B, T, Ts, seed=seed, id_offset=id_offset, **gen_kw)
         return res["X"], res["U"], None
 
     r = _run_rank(run, B, out_prefix, dist, shards, lambda prefix, X, U, st, ids: _write_xu(
-        prefix, X, U, ids, Ts, device_csv))
+        prefix, X, U, ids, Ts, device_csv, device_noise=device_noise))
     return None if r is None else r[:2]
 
 
-def generate_open_loop(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shards=False, device_csv=False):
+def generate_open_loop(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shards=False, device_csv=False,
+                       device_noise=False):
     """The reference's own dataset (generation_traj/generation_type1.py:240-339), B trajectories of T steps per rank:
     this rank's ids rank * B .. rank * B + B - 1 of the dataset seeded with `seed` (generation_type1.generate_steps:
     host draw, one kernel launch), gathered to rank 0, which writes ``{out_prefix}_clean.csv`` /
     ``{out_prefix}_noisy.csv`` (write_csv).  No status sidecar: the reference has none and no step can fail.
     shards: no gather, every rank writes ``{out_prefix}_rank{r}_*.csv`` with its global ids.
     device_csv: opt-in (default False) -- the files' text is formatted on the GPU (write_csv_device, the same bytes).
+    device_noise: opt-in, with device_csv only (ValueError otherwise) -- the measurement noise is drawn on the GPU too.
     Returns (X [W B,T+1,6], U [W B,T,2]) on rank 0 and None on the other ranks (shards: this rank's share)."""
     from ..generation_type1 import generate_steps
-    return _generate_xu(generate_steps, B, T, Ts, seed, out_prefix, dist, shards, device_csv)
+    return _generate_xu(generate_steps, B, T, Ts, seed, out_prefix, dist, shards, device_csv, device_noise)
 
 
-def generate_piecewise(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shards=False, device_csv=False):
+def generate_piecewise(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shards=False, device_csv=False,
+                       device_noise=False, device_seed=False):
     """The reference's second dataset (generation_traj/generation_type2.py:162-220, :290-322), B trajectories of T
     steps per rank: this rank's ids rank * B .. rank * B + B - 1 of the dataset seeded with `seed`
     (generation_type2.generate_steps: the controller, its random streams and the simulation in one kernel launch),
@@ -169,9 +182,12 @@ def generate_piecewise(B, T, Ts=0.01, seed=42, out_prefix=None, dist=None, shard
     reference's noise seeds 12345 + id, sigmas and columns; mode strings are not written, the reference drops them).
     shards: no gather, every rank writes ``{out_prefix}_rank{r}_*.csv`` with its global ids.
     device_csv: opt-in (default False) -- the files' text is formatted on the GPU (write_csv_device, the same bytes).
+    device_noise: opt-in, with device_csv only (ValueError otherwise) -- the measurement noise is drawn on the GPU too.
+    device_seed: opt-in -- the trajectories' generator states are seeded on the GPU (generation_type2.pcg64_states).
     Returns (X [W B,T+1,6], U [W B,T,2]) on rank 0 and None on the other ranks (shards: this rank's share)."""
     from ..generation_type2 import generate_steps
-    return _generate_xu(generate_steps, B, T, Ts, seed, out_prefix, dist, shards, device_csv)
+    return _generate_xu(generate_steps, B, T, Ts, seed, out_prefix, dist, shards, device_csv, device_noise,
+                        device_seed=device_seed)
 
 
 def merge_datasets(first_prefix, second_prefix, out_prefix):
@@ -218,17 +234,18 @@ def merge_datasets(first_prefix, second_prefix, out_prefix):
     return id_offset
 
 
-def _write_xu(prefix, X, U, ids, Ts, device_csv, noise_ids=None):
+def _write_xu(prefix, X, U, ids, Ts, device_csv, noise_ids=None, device_noise=False):
     """The two CSVs of X, U (device tensors, or host arrays with device_csv=False): through the host writer (the
-    default) or formatted on the GPU."""
+    default) or formatted on the GPU (device_noise: with the noise drawn there too)."""
+    _check_device_noise(device_csv, device_noise)
     if device_csv:
-        write_csv_device(prefix, X, U, ids, Ts, noise_ids=noise_ids)
+        write_csv_device(prefix, X, U, ids, Ts, noise_ids=noise_ids, device_noise=device_noise)
     else:
         host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else a   # noqa: E731
         write_csv(prefix, host(X), host(U), ids, Ts, noise_ids=noise_ids)
 
 
-def _write_with_sidecar(prefix, X, U, st, ids, Ts, drop_failed, device_csv=False):
+def _write_with_sidecar(prefix, X, U, st, ids, Ts, drop_failed, device_csv=False, device_noise=False):
     """CSVs + status sidecar of trajectories `ids` (generation ids); drop_failed re-indexes the kept ones."""
     sth = st.cpu().numpy() if hasattr(st, "cpu") else np.asarray(st)
     ids = np.asarray(ids, dtype=np.int64)
@@ -246,5 +263,5 @@ def _write_with_sidecar(prefix, X, U, st, ids, Ts, drop_failed, device_csv=False
         else:
             X, U = X[keep], U[keep]
         sth, source_ids, ids = sth[:, keep], ids[keep], np.arange(keep.size, dtype=np.int64)
-    _write_xu(prefix, X, U, ids, Ts, device_csv, noise_ids=source_ids)
+    _write_xu(prefix, X, U, ids, Ts, device_csv, noise_ids=source_ids, device_noise=device_noise)
     write_status_csv(prefix, sth, ids, source_ids=source_ids)

@@ -8,7 +8,8 @@ Euler integration of all trajectories on the GPU, one lane per trajectory.  Plot
 
 The single-trajectory functions run on the host in numpy with np.random.default_rng; they are the specification the
 kernel is tested against.  Nothing sequential is left on the host: every trajectory has a stream of its own
-(default_rng(seed + i)), whose PCG64 state the kernel takes over (pcg64_states), and the one shared stream, the x0
+(default_rng(seed + i)), whose PCG64 state the kernel takes over (pcg64_states: numpy's SeedSequence on the host, or
+csrc/seed_seq.h on the GPU), and the one shared stream, the x0
 draw from default_rng(seed), takes exactly six uniforms per trajectory, so a shard jumps to its place in it
 (draw_x0: PCG64.advance, nothing drawn and discarded).
 """
@@ -183,20 +184,49 @@ def pcg64_state_words(bit_generator):
     return np.array([s["state"] >> 64, s["state"] & m, s["inc"] >> 64, s["inc"] & m], dtype=np.uint64)
 
 
-def pcg64_states(seeds):
-    """[n,4] uint64: the states of np.random.default_rng(s) for s in seeds (SeedSequence runs here, on the host)."""
-    return np.array([pcg64_state_words(np.random.PCG64(int(s))) for s in seeds], dtype=np.uint64).reshape(-1, 4)
+def seed_entropy_words(seeds):
+    """[n,nwords] uint32: the ints in seeds as numpy's SeedSequence coerces them -- little-endian 32-bit words, at least
+    one -- padded with zero words to the longest (which changes no state while nwords <= 4, csrc/seed_seq.h).
+    ValueError for a negative seed, as numpy raises, and for one of more than 128 bits."""
+    vals = [int(s) for s in seeds]
+    if any(v < 0 for v in vals):
+        raise ValueError("expected non-negative integer")      # numpy's words
+    nwords = max([1] + [(v.bit_length() + 31) // 32 for v in vals])
+    if nwords > 4:
+        raise ValueError("seed_entropy_words: seeds of more than 128 bits cannot be zero-padded to a common length")
+    return np.array([[(v >> (32 * k)) & 0xffffffff for k in range(nwords)] for v in vals],
+                    dtype=np.uint32).reshape(-1, nwords)
 
 
-def generate_steps(num_traj, steps, Ts=0.01, seed=2025, id_offset=0, rules=None, device=None, want_rng_state=False):
-    """generate_dataset with the length given in steps."""
+def pcg64_states(seeds, device=None):
+    """[n,4] uint64: the states of np.random.default_rng(s) for s in seeds.  device None: numpy's SeedSequence on the
+    host, a numpy array.  With a device: seeded there (traj_gen_seed_pcg64_batch, csrc/seed_seq.h, the same words) and
+    returned as an int64 CUDA tensor [n,4] holding the bits of the uint64 words."""
+    if device is None:
+        return np.array([pcg64_state_words(np.random.PCG64(int(s))) for s in seeds], dtype=np.uint64).reshape(-1, 4)
+    import torch
+
+    from . import _lib
+    ent = seed_entropy_words(seeds)
+    with torch.cuda.device(device):
+        ent_d = torch.from_numpy(ent.view(np.int32)).to(device)
+        states = torch.empty((ent.shape[0], 4), dtype=torch.int64, device=device)
+        _lib.check(_lib.lib().traj_gen_seed_pcg64_batch(_lib.ptr(ent_d), ent.shape[0], ent.shape[1], _lib.ptr(states),
+                                                        _lib.stream()), "traj_gen_seed_pcg64_batch")
+    return states
+
+
+def generate_steps(num_traj, steps, Ts=0.01, seed=2025, id_offset=0, rules=None, device=None, want_rng_state=False,
+                   device_seed=False):
+    """generate_dataset with the length given in steps.  device_seed: the per-trajectory generator states are seeded on
+    the GPU (pcg64_states with a device) instead of by numpy on the host; the shared x0 stream stays on the host."""
     import torch
 
     from . import batch as TB
     dev = TB.require_gpu(device)
     ids = np.arange(id_offset, id_offset + num_traj)
     x0 = draw_x0(num_traj, seed, id_offset)
-    states = pcg64_states(seed + ids)
+    states = pcg64_states([int(seed) + int(i) for i in ids], dev if device_seed else None)
     with torch.cuda.device(dev):
         out = TB.simulate_piecewise(torch.as_tensor(x0, device=dev), states, steps, Ts, rules, Params,
                                     want_rng_state=want_rng_state)
