@@ -1,4 +1,4 @@
-"""The arithmetic of knet_fc2x_kernel (csrc/knet.hip) restated in numpy: a float32 value split into three bf16
+"""The arithmetic of knet_fc2x_kernel (csrc/knet_fc2.h) restated in numpy: a float32 value split into three bf16
 terms (each rounded to nearest even, the residuals formed in float32) is represented exactly, and the six kept
 term products of a b differ from the exact product by less than 2^-23 |a b|, the size of one float32 rounding of
 the product.  CPU only; the GPU kernel itself is checked against float64 in tests/test_knet_fc2.py."""

@@ -1,4 +1,4 @@
-"""Every KalmanNet kernel of csrc/knet.hip on its own against the float64 reference of tests/_knet_ref.py:
+"""Every KalmanNet kernel of csrc/knet.hip (its stage headers csrc/knet_*.h) on its own against the float64 reference of tests/_knet_ref.py:
 the stand-alone ops (trajknet::prior / gru_gates / update), each stage of the fused step (front / FC2 / back and the
 merged back+front launch) teacher-forced from the GPU's own upstream outputs, the EKF across a launch block, batch
 independence and NaN isolation of the fused runner, the forward / backward pairing of the training ops, and the

@@ -1,5 +1,6 @@
 #!/bin/bash
-# KalmanNet bench leg (tools/knet_bench.py) for every library build under _variants/*/.
+# KalmanNet bench leg (tools/knet_bench.py) for every library build under _variants/*/ (each a libtrajmpc.so
+# built by hand, e.g. `make OUT=../../_variants/NAME/libtrajmpc.so OBJDIR=../../_variants/NAME/_build EXTRA=...`).
 cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 for d in _variants/*/; do
