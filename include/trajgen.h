@@ -173,6 +173,57 @@ int traj_gen_seed_pcg64_host(const uint32_t* entropy /*[B,nwords]*/, int B, int 
 int traj_gen_seed_pcg64_batch(const uint32_t* entropy /*[B,nwords]*/, int B, int nwords,
                               unsigned long long* states /*[B,4]*/, void* stream);
 
+/* ---- the closed loop's workload and its spline paths built on the device (csrc/workload.hip, csrc/spline.h) ----
+ *
+ * Natural cubic spline piece coefficients (batch.spline_natural's columns) of B trajectories, one lane per trajectory:
+ * what PathSet.build computes in a Python loop.  kind [B] (traj_paths' codes: 2 = spline), nk [B] knots per trajectory,
+ * xk / yk [B,kmax] knot abscissae / ordinates -> coef [B,kmax-1,4], flag [B].
+ * A kind-2 row gets its nk - 1 pieces (second derivatives by the Thomas algorithm; nk = 2: the chord) and zeros after
+ * them; a row of another kind is all zeros.  A kind-2 row with nk < 2, nk > kmax, knots that do not strictly increase
+ * or a knot or ordinate that is not finite gets flag[b] = 1 and zeros; every other row flag[b] = 0.
+ * _host: host pointers, synchronous, the same text on the CPU -- the same bits.  _batch: device pointers, asynchronous.
+ * TRAJ_E_ARG: B < 1, kmax < 2, a null pointer. */
+int traj_gen_spline_coef_host(int B, int kmax, const int* kind /*[B]*/, const int* nk /*[B]*/,
+                              const double* xk /*[B,kmax]*/, const double* yk /*[B,kmax]*/,
+                              double* coef /*[B,kmax-1,4]*/, int* flag /*[B]*/);
+int traj_gen_spline_coef_batch(int B, int kmax, const int* kind /*[B]*/, const int* nk /*[B]*/,
+                               const double* xk /*[B,kmax]*/, const double* yk /*[B,kmax]*/,
+                               double* coef /*[B,kmax-1,4]*/, int* flag /*[B]*/, void* stream);
+
+/* workload.make_workload's three kinds, and the spline kind's knot abscissae xk[i] = X0 + DX i (SPLINE_KNOTS_X). */
+#define TRAJ_WORKLOAD_SPLINE   0
+#define TRAJ_WORKLOAD_MIXED    1
+#define TRAJ_WORKLOAD_PARABOLA 2
+#define TRAJ_WORKLOAD_SPLINE_KNOTS 11
+#define TRAJ_WORKLOAD_SPLINE_X0 (-6.0)
+#define TRAJ_WORKLOAD_SPLINE_DX 4.0
+#define TRAJ_WORKLOAD_MAX_SEED_WORDS 6   /* + tid's two = csrc/seed_seq.h's SEED_SEQ_MAX_WORDS */
+
+/* make_workload's loop body for the trajectories tid = id_offset + b, b < B, one lane per trajectory: the stream
+ * np.random.default_rng([seed, tid]) (entropy: seed_words[0 .. ns), the seed's uint32 words as numpy coerces it, little
+ * end first and at least one -- a HOST pointer, read before the call returns -- followed by tid's one word, or two from
+ * 2^32 on), its uniform draws in make_workload's order, the path they describe and the initial state on it:
+ *   spline    11 knot ordinates in (-1, 1), kind 2, nk = 11, the coefficients as traj_gen_spline_coef_batch forms them
+ *   mixed     even tid: A, w, phase -> kind 1, pc = (A, w, phase, 0);  odd tid: a -> kind 0, pc = (0, 0, a, 0)
+ *   parabola  no draw: kind 0, pc = (0, 0, 0.1, 0), x0 = (0, 0.5, 0, 1, 0, 0) (MPC/main.py:77)
+ *   x0        draws X, dY, dphi, vx, vy, omega: (X, y(X) + dY, atan(y'(X)) + dphi, vx, vy, omega), y and y' by the rule
+ *             the closed loop applies to the row (path_eval)
+ *   u0        ((Cr0 + Cr2 vx vx) / (Cm1 - Cm2 vx), 0)  (MPC/main.py:9-22)
+ * Outputs: kind [B], pc [B,4], nk [B] (0 off the spline kind), xk / yk [B,kmax] and coef [B,kmax-1,4] (zeros past the
+ * knots and off the spline kind), x0 [B,6], u0 [B,2]: traj_paths' arrays plus the closed loop's initial state.
+ * _host: host pointers, synchronous, the same text on the CPU: the same bits except where libm enters (atan in phi;
+ * sin / cos in a sinusoid row's Y and phi).  _batch: device pointers (but seed_words), asynchronous on `stream`.
+ * TRAJ_E_ARG: a null pointer, an unknown workload, ns outside 1 .. TRAJ_WORKLOAD_MAX_SEED_WORDS, B < 1, id_offset < 0
+ * or id_offset + B past 2^63 - 1, kmax < 2 (spline: < TRAJ_WORKLOAD_SPLINE_KNOTS). */
+int traj_gen_workload_host(const traj_vehicle_params* p, int workload, const uint32_t* seed_words /*[ns]*/, int ns,
+                           long long id_offset, int B, int kmax, int* kind /*[B]*/, double* pc /*[B,4]*/,
+                           int* nk /*[B]*/, double* xk /*[B,kmax]*/, double* yk /*[B,kmax]*/,
+                           double* coef /*[B,kmax-1,4]*/, double* x0 /*[B,6]*/, double* u0 /*[B,2]*/);
+int traj_gen_workload_batch(const traj_vehicle_params* p, int workload, const uint32_t* seed_words /*[ns]*/, int ns,
+                            long long id_offset, int B, int kmax, int* kind /*[B]*/, double* pc /*[B,4]*/,
+                            int* nk /*[B]*/, double* xk /*[B,kmax]*/, double* yk /*[B,kmax]*/,
+                            double* coef /*[B,kmax-1,4]*/, double* x0 /*[B,6]*/, double* u0 /*[B,2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

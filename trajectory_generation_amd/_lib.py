@@ -119,6 +119,9 @@ RNG_RAW, RNG_DOUBLE, RNG_NORMAL = 0, 1, 2                    # TRAJ_RNG_*
 GEN_STAGE_STEPS = 8                                          # TRAJ_GEN_STAGE_STEPS
 GEN_FORM_DEFAULT, GEN_FORM_STAGED, GEN_FORM_DIRECT = 0, 1, 2  # traj_gen_debug_store_form
 GEN_DEFAULT_FORM = GEN_FORM_DIRECT                           # TRAJ_GEN_DEFAULT_FORM
+WORKLOADS = {"spline": 0, "mixed": 1, "parabola": 2}         # TRAJ_WORKLOAD_*
+WORKLOAD_SPLINE_KNOTS = 11                                   # TRAJ_WORKLOAD_SPLINE_KNOTS
+WORKLOAD_MAX_SEED_WORDS = 6                                  # TRAJ_WORKLOAD_MAX_SEED_WORDS
 
 
 class Paths(C.Structure):
@@ -239,6 +242,12 @@ _SIGS = {
     "traj_gen_rng_draw_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _V, _V, _V, _V]),
     "traj_gen_seed_pcg64_host": (C.c_int, [_V, C.c_int, C.c_int, _V]),
     "traj_gen_seed_pcg64_batch": (C.c_int, [_V, C.c_int, C.c_int, _V, _V]),
+    "traj_gen_spline_coef_host": (C.c_int, [C.c_int, C.c_int, _V, _V, _V, _V, _V, _V]),
+    "traj_gen_spline_coef_batch": (C.c_int, [C.c_int, C.c_int, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_gen_workload_host": (C.c_int, [C.POINTER(VehicleParams), C.c_int, _V, C.c_int, C.c_longlong, C.c_int, C.c_int,
+                                         _V, _V, _V, _V, _V, _V, _V, _V]),
+    "traj_gen_workload_batch": (C.c_int, [C.POINTER(VehicleParams), C.c_int, _V, C.c_int, C.c_longlong, C.c_int,
+                                          C.c_int, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "traj_closed_loop_step": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
                                         _V, _V, _V, C.c_int, C.c_int, _V, _V, _V, _V, _V, C.c_size_t, _V]),
     "traj_closed_loop_run": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,

@@ -391,6 +391,69 @@ def spline_natural(xk, yk):
     return coef
 
 
+def spline_natural_stacked(xk, yk):
+    """spline_natural for G knot sets of one length at once: xk, yk [G,n] -> coef [G,n-1,4].  The same systems, filled
+    with array operations, go through one np.linalg.solve on the stacked [G,n-2,n-2] matrices (LAPACK factors each
+    matrix as the per-matrix call does), and the columns are spline_natural's expressions: the same bits
+    (tests/test_workload_host.py holds that)."""
+    xk = np.asarray(xk, dtype=np.float64)
+    yk = np.asarray(yk, dtype=np.float64)
+    G, n = xk.shape
+    h = np.diff(xk, axis=1)
+    M = np.zeros((G, n))
+    if n > 2:
+        A = np.zeros((G, n - 2, n - 2))
+        r = np.arange(n - 2)
+        A[:, r, r] = 2.0 * (h[:, :-1] + h[:, 1:])
+        A[:, r[1:], r[:-1]] = h[:, 1:-1]
+        A[:, r[:-1], r[1:]] = h[:, 1:-1]
+        rhs = 6.0 * ((yk[:, 2:] - yk[:, 1:-1]) / h[:, 1:] - (yk[:, 1:-1] - yk[:, :-2]) / h[:, :-1])
+        M[:, 1:-1] = np.linalg.solve(A, rhs[:, :, None])[:, :, 0]
+    coef = np.zeros((G, n - 1, 4))
+    coef[:, :, 0] = yk[:, :-1]
+    coef[:, :, 1] = (yk[:, 1:] - yk[:, :-1]) / h - h * (2.0 * M[:, :-1] + M[:, 1:]) / 6.0
+    coef[:, :, 2] = M[:, :-1] / 2.0
+    coef[:, :, 3] = (M[:, 1:] - M[:, :-1]) / (6.0 * h)
+    return coef
+
+
+def spline_rows(kinds, knots, kmax):
+    """PathSet.build's host arrays (nk [B], xk [B,kmax], coef [B,kmax-1,4]): the kind-2 trajectories grouped by knot
+    count, one spline_natural_stacked per group; zeros elsewhere."""
+    kinds = np.asarray(kinds)
+    B = len(kinds)
+    xk = np.zeros((B, kmax))
+    coef = np.zeros((B, kmax - 1, 4))
+    nk = np.zeros(B, np.int32)
+    idx = np.nonzero(kinds == 2)[0]
+    lens = np.array([len(knots[b][0]) for b in idx], dtype=np.int64)
+    for n in np.unique(lens):
+        g = idx[lens == n]
+        kx = np.array([knots[b][0] for b in g], dtype=np.float64).reshape(len(g), n)
+        ky = np.array([knots[b][1] for b in g], dtype=np.float64).reshape(len(g), n)
+        nk[g] = n
+        xk[g, :n] = kx
+        coef[g, :n - 1] = spline_natural_stacked(kx, ky)
+    return nk, xk, coef
+
+
+def spline_coef_host(kinds, nk, xk, yk):
+    """csrc/spline.h on the CPU (traj_gen_spline_coef_host): kinds [B], nk [B], xk / yk [B,kmax] -> numpy
+    (coef [B,kmax-1,4], flag [B]), the arrays PathSet.build_device computes on the GPU, bit for bit."""
+    kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+    nk = np.ascontiguousarray(nk, dtype=np.int32)
+    xk = np.ascontiguousarray(xk, dtype=np.float64)
+    yk = np.ascontiguousarray(yk, dtype=np.float64)
+    B, kmax = xk.shape
+    if kinds.shape != (B,) or nk.shape != (B,) or yk.shape != (B, kmax):
+        raise ValueError(f"kinds, nk must be [B] and yk [B,kmax] with xk's B = {B}, kmax = {kmax}")
+    coef = np.empty((B, max(kmax - 1, 0), 4))
+    flag = np.empty(B, dtype=np.int32)
+    _lib.check(_lib.lib().traj_gen_spline_coef_host(B, kmax, _p(kinds), _p(nk), _p(xk), _p(yk), _p(coef), _p(flag)),
+               "traj_gen_spline_coef_host")
+    return coef, flag
+
+
 @dataclass
 class PathSet:
     """Per-trajectory reference geometry on the device (traj_paths).
@@ -420,19 +483,41 @@ class PathSet:
         dev = require_gpu(device)
         B = len(kinds)
         kmax = max([2] + [len(k[0]) for k in (knots or []) if k is not None])
-        xk = np.zeros((B, kmax))
-        coef = np.zeros((B, kmax - 1, 4))
-        nk = np.zeros(B, np.int32)
-        for b in range(B):
-            if kinds[b] == 2:
-                kx, ky = knots[b]
-                nk[b] = len(kx)
-                xk[b, :len(kx)] = kx
-                coef[b, :len(kx) - 1] = spline_natural(kx, ky)
+        nk, xk, coef = spline_rows(kinds, knots, kmax)
         return PathSet(kind=torch.as_tensor(np.asarray(kinds, np.int32), device=dev),
                        pc=torch.as_tensor(np.asarray(pcs, np.float64).reshape(B, 4), device=dev),
                        nk=torch.as_tensor(nk, device=dev), xk=torch.as_tensor(xk, device=dev),
                        coef=torch.as_tensor(coef, device=dev))
+
+    @staticmethod
+    def build_device(kinds, pcs, nk, xk, yk, device=None, check=True) -> "PathSet":
+        """build from arrays, the coefficients computed on the GPU (traj_gen_spline_coef_batch, csrc/spline.h): kinds
+        [B], pcs [B,4], nk [B] knots per trajectory, xk / yk [B,kmax] knot abscissae / ordinates (tensors or arrays;
+        rows of kind 0 / 1 and entries past nk are not read).  No host loop.  The coefficients agree with build's to rounding
+        (Thomas algorithm against LAPACK's LU), not bit for bit.
+        check: read the kernel's flags back (synchronizes) and raise ValueError naming the first kind-2 trajectory with
+        nk < 2, nk > kmax, knots that do not strictly increase or a value that is not finite."""
+        dev = require_gpu(device)
+        kind = torch.as_tensor(kinds, dtype=torch.int32, device=dev).reshape(-1).contiguous()
+        B = kind.shape[0]
+        nk = torch.as_tensor(nk, dtype=torch.int32, device=dev).reshape(-1).contiguous()
+        xk = _dev(xk, None, dev)
+        yk = _dev(yk, None, dev)
+        if xk.dim() != 2 or xk.shape[0] != B or xk.shape[1] < 2 or yk.shape != xk.shape or nk.shape[0] != B:
+            raise ValueError(f"xk, yk must be [B,kmax] with B = {B}, kmax >= 2 and nk [B]; got {tuple(xk.shape)}, "
+                             f"{tuple(yk.shape)}, {tuple(nk.shape)}")
+        kmax = xk.shape[1]
+        coef = torch.empty((B, kmax - 1, 4), dtype=torch.float64, device=dev)
+        flag = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().traj_gen_spline_coef_batch(B, kmax, _p(kind), _p(nk), _p(xk), _p(yk), _p(coef), _p(flag),
+                                                         _stream()), "traj_gen_spline_coef_batch")
+        if check:
+            bad = torch.nonzero(flag)
+            if bad.numel():
+                b = int(bad[0])
+                raise ValueError(f"PathSet.build_device: trajectory {b}: nk = {int(nk[b])} with kmax = {kmax}, or its "
+                                 "knots do not strictly increase, or a knot or ordinate is not finite")
+        return PathSet(kind=kind, pc=_dev(pcs, (B, 4), dev), nk=nk, xk=xk, coef=coef)
 
 
 def ref_window_batch(paths: PathSet, x_start, vref, N, Ts) -> torch.Tensor:

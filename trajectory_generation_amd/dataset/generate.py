@@ -75,7 +75,9 @@ def write_status_csv(out_prefix, status, ids, source_ids=None):
 def _closed_loop_gpu(w, T, cfg):
     """This rank's closed loop on the GPU (batch.run_closed_loop, fused launch)."""
     from .. import batch as TB
-    paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
+    paths = w.get("paths")      # make_workload_device built them with the workload
+    if paths is None:
+        paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
     return TB.run_closed_loop(w["x0"], w["u0"], paths, w["vref"], T, cfg)
 
 
@@ -100,7 +102,8 @@ def _run_rank(run, B, out_prefix, dist, shards, write):
 
 
 def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=None, polish_mode=0,
-             closed_loop=None, drop_failed=False, shards=False, device_csv=False, device_noise=False):
+             closed_loop=None, drop_failed=False, shards=False, device_csv=False, device_noise=False,
+             device_workload=False):
     """Run the closed loop for this rank's B trajectories (ids rank * B .. rank * B + B - 1), gather the
     histories to rank 0 and (rank 0) write ``{out_prefix}_clean.csv`` / ``{out_prefix}_noisy.csv`` and the
     status sidecar ``{out_prefix}_status.csv`` (write_status_csv).
@@ -120,10 +123,15 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
       device tensors (write_csv_device, the same bytes).
     device_noise: opt-in, with device_csv only (ValueError otherwise) -- the noisy file's measurement noise is drawn on
       the GPU too (measurement_noise_device, the same bits).
+    device_workload: opt-in (default False: workload.make_workload, the specification) -- this rank's workload and its
+      PathSet are built on the GPU in one launch (workload.make_workload_device: the same draws; Y, phi and the spline
+      coefficients to rounding, so the trajectories are not the host-built workload's bit for bit).  closed_loop gets
+      that dict: device tensors, knots=None, the PathSet under "paths".
     Returns (X [W B,T+1,6], U [W B,T,2], status [T,W B]) on rank 0 and None on the other ranks (shards:
     this rank's (X, U, status) everywhere)."""
-    from ..workload import make_workload
+    from ..workload import make_workload, make_workload_device
     _check_device_noise(device_csv, device_noise)
+    build = make_workload_device if device_workload else make_workload
     cfg = None
     if closed_loop is None:
         from .. import batch as TB
@@ -133,7 +141,7 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
         raise ValueError("drop_failed re-indexes the whole dataset: it needs the gather (shards=False)")
 
     def run(id_offset):
-        res = closed_loop(make_workload(B, N, Ts, kind=kind, seed=seed, id_offset=id_offset), T, cfg)
+        res = closed_loop(build(B, N, Ts, kind=kind, seed=seed, id_offset=id_offset), T, cfg)
         return res["X"], res["U"], res["status"]
 
     return _run_rank(run, B, out_prefix, dist, shards, lambda prefix, X, U, st, ids: _write_with_sidecar(

@@ -30,17 +30,22 @@ import torch
 from . import batch as TB
 from .dataset import measurement_noise
 from .knet_train import EPS_DB, PHI_IDX, loss_x_with_angular
-from .workload import make_workload
+from .workload import make_workload, make_workload_device
 
 TRAIN_ID_OFFSET = 1 << 20   # ids of the normalization ("train") draw: disjoint from the test ids
 OBS_IDX = (0, 1, 3, 4, 5)   # vehicle_model.py:149-150 (h), data_loader.py noisy columns
 
 
-def make_sequences(B, T, Ts=0.01, N=20, seed=0, id_offset=0, device=None):
+def make_sequences(B, T, Ts=0.01, N=20, seed=0, id_offset=0, device=None, device_workload=False):
     """B closed-loop trajectories of T rows at plant step Ts -> dict of float32 tensors y [B,5,T]
-    (noisy, real units), u [B,2,T], x [B,6,T] (clean), on the GPU."""
-    w = make_workload(B, N, Ts, kind="spline", seed=seed, id_offset=id_offset)
-    paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"], device=device)
+    (noisy, real units), u [B,2,T], x [B,6,T] (clean), on the GPU.  device_workload: opt-in, the workload and its
+    paths built on the GPU (workload.make_workload_device)."""
+    if device_workload:
+        w = make_workload_device(B, N, Ts, kind="spline", seed=seed, id_offset=id_offset, device=device)
+        paths = w["paths"]
+    else:
+        w = make_workload(B, N, Ts, kind="spline", seed=seed, id_offset=id_offset)
+        paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"], device=device)
     res = TB.run_closed_loop(w["x0"], w["u0"], paths, w["vref"], T, TB.config_struct(N=N, Ts=Ts))
     X = res["X"][:, :T]                                    # rows 0 .. T-1 (data_loader.py:41-53)
     U = res["U"][:, :T]

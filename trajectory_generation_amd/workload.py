@@ -18,6 +18,8 @@ omega ~ U(-1, 1); u_prev = [d_ss(vx), 0] (main.py:20-22).  vref = the main.py:28
 (0.8 -> 2.0 m/s over 2 s) over the horizon, re-used every step (main.py:87).
 Trajectory `tid` draws from numpy.random.default_rng([seed, tid]) so shards are reproducible
 for any rank count.
+make_workload is the specification; make_workload_device builds the same workload and its PathSet on the GPU in
+one launch (csrc/workload.hip: the same streams and draws, no per-trajectory Python), opt-in.
 """
 from __future__ import annotations
 
@@ -86,4 +88,72 @@ def make_workload(B, N=20, Ts=0.05, kind="spline", seed=0, id_offset=0):
     u0 = np.stack([np.array([d_steady_state(v), 0.0]) for v in x0[:, 3]])
     return dict(kinds=np.array(kinds, np.int32), pcs=np.array(pcs, np.float64), knots=knots, x0=x0, u0=u0,
                 vref=vref_ramp(N, Ts), ids=np.arange(id_offset, id_offset + B))
+
+
+def _workload_args(B, kind, seed, id_offset):
+    """(workload code, seed words uint32 [ns], kmax) of the library's workload builders, refusing what
+    numpy.random.default_rng([seed, tid]) refuses (a negative int) and what the library does not take."""
+    from . import _lib
+    if kind not in _lib.WORKLOADS:
+        raise ValueError(kind)
+    seed, id_offset = int(seed), int(id_offset)
+    if seed < 0 or id_offset < 0:
+        raise ValueError("expected non-negative integer")      # numpy's words
+    ns = max(1, (seed.bit_length() + 31) // 32)
+    if ns > _lib.WORKLOAD_MAX_SEED_WORDS:
+        raise ValueError(f"seed has {ns} 32-bit words; the device builder takes {_lib.WORKLOAD_MAX_SEED_WORDS}")
+    if int(B) < 1 or id_offset + int(B) > 2 ** 63 - 1:
+        raise ValueError(f"B = {B}, id_offset = {id_offset}: need B >= 1 and ids below 2^63")
+    words = np.array([(seed >> (32 * k)) & 0xffffffff for k in range(ns)], dtype=np.uint32)
+    return _lib.WORKLOADS[kind], words, (_lib.WORKLOAD_SPLINE_KNOTS if kind == "spline" else 2)
+
+
+def workload_rows_host(B, kind="spline", seed=0, id_offset=0, params=None):
+    """make_workload's loop on the CPU through the library (traj_gen_workload_host: the text of the GPU builder,
+    csrc/workload.hip).  Returns numpy arrays kinds [B], pcs [B,4], nk [B], xk / yk [B,kmax], coef [B,kmax-1,4],
+    x0 [B,6], u0 [B,2].  For the tests; make_workload stays the specification."""
+    import ctypes as C
+
+    from . import _lib
+    from .batch import params_struct
+    code, words, kmax = _workload_args(B, kind, seed, id_offset)
+    B = int(B)
+    o = dict(kinds=np.empty(B, np.int32), pcs=np.empty((B, 4)), nk=np.empty(B, np.int32), xk=np.empty((B, kmax)),
+             yk=np.empty((B, kmax)), coef=np.empty((B, kmax - 1, 4)), x0=np.empty((B, 6)), u0=np.empty((B, 2)))
+    _lib.check(_lib.lib().traj_gen_workload_host(C.byref(params_struct(params)), code, _lib.ptr(words), len(words),
+                                                 int(id_offset), B, kmax, *[_lib.ptr(a) for a in o.values()]),
+               "traj_gen_workload_host")
+    return o
+
+
+def make_workload_device(B, N=20, Ts=0.05, kind="spline", seed=0, id_offset=0, device=None, params=None):
+    """make_workload built on the GPU in one launch (traj_gen_workload_batch): no per-trajectory Python.
+
+    Returns make_workload's keys with kinds [B], pcs [B,4], x0 [B,6], u0 [B,2] as device tensors, knots=None,
+    yk [B,kmax] (the spline kind's knot ordinates; zeros otherwise) and paths, the PathSet of the workload (its
+    coefficients by csrc/spline.h); vref [N+1] and ids [B] stay numpy.  The draws, kinds, pcs, knots, X, vx, vy, omega
+    are make_workload's bit for bit; u0 within 2 ulp (v * v against the host's v ** 2); Y, phi and the coefficients to
+    rounding (Thomas against LAPACK, the device's atan and sincos against the host's).  params: vehicle parameters of
+    u0's steady-state throttle (default: the reference's, as make_workload).  ValueError for a negative seed or
+    id_offset, as numpy raises, and for a seed of more than six 32-bit words."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from .batch import PathSet, params_struct, require_gpu
+    dev = require_gpu(device)
+    code, words, kmax = _workload_args(B, kind, seed, id_offset)
+    B = int(B)
+    f64 = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    kinds, nk = torch.empty(B, **i32), torch.empty(B, **i32)
+    pcs, xk, yk = torch.empty((B, 4), **f64), torch.empty((B, kmax), **f64), torch.empty((B, kmax), **f64)
+    coef, x0, u0 = torch.empty((B, kmax - 1, 4), **f64), torch.empty((B, 6), **f64), torch.empty((B, 2), **f64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().traj_gen_workload_batch(
+            C.byref(params_struct(params)), code, _lib.ptr(words), len(words), int(id_offset), B, kmax,
+            *[_lib.ptr(t) for t in (kinds, pcs, nk, xk, yk, coef, x0, u0)], _lib.stream()), "traj_gen_workload_batch")
+    return dict(kinds=kinds, pcs=pcs, knots=None, yk=yk, x0=x0, u0=u0, vref=vref_ramp(N, Ts),
+                ids=np.arange(id_offset, id_offset + B), paths=PathSet(kind=kinds, pc=pcs, nk=nk, xk=xk, coef=coef))
 
