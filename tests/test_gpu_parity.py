@@ -959,6 +959,61 @@ def test_closed_loop_state_bounds_per_step(gpu, oracle_lib, N, Ts, T, B, bounds)
           f"{np.nanmax(X[:, :, 3]):.3f} (unbounded {np.nanmax(un['X'].cpu().numpy()[:, :, 3]):.3f})")
 
 
+def test_closed_loop_step_small_horizon_both_tiers(gpu):
+    """The plant update the general tier's per-step path shares with the condensed kernels (csrc/mpc_frame.h:
+    closed_sb_plant_kernel is plant_update), next to the window of ref_window_kernel that feeds it: 3
+    traj_closed_loop_step calls at N = 4, B = 5, spline paths, once with one finite state bound that is never active
+    (vx <= 1e3: the general solver) and once without bounds (the register-resident kernel).  Each run's history row
+    t + 1 is bit for bit the state the step leaves in place (and row t of hist_u the u_prev it leaves).  The two runs
+    agree at test_closed_loop_state_bounds_per_step's bars for two solvers of one problem, on every one of the 15
+    (step, instance) pairs -- the bound is never active, so none is exempt: the statuses are equal and every step is
+    either polished on both tiers (the applied u to 1e-6) or on neither at the same iteration count (1e-4) -- and the
+    state rows, which integrate those commands (x' = x + Ts f(x, u)), at the loosest bar a command that fed them was
+    held to."""
+    from trajectory_generation_amd.workload import make_workload
+    N, Ts, T, B = 4, 0.02, 3, 5
+    w = make_workload(B, N, Ts, kind="spline", seed=5)
+    paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
+    vr = torch.as_tensor(np.tile(w["vref"], (B, 1)), dtype=torch.float64, device="cuda").contiguous()
+    runs = {}
+    for name, x_hi in (("bounded", [np.inf, np.inf, np.inf, 1e3, np.inf, np.inf]), ("none", None)):
+        kw = dict(x_lo=[-np.inf] * 6, x_hi=x_hi) if x_hi else {}
+        cfg = TB.config_struct(N=N, Ts=Ts, warm_start=0, **kw)
+        x = torch.as_tensor(w["x0"], dtype=torch.float64, device="cuda").reshape(B, 6).clone()
+        u = torch.as_tensor(w["u0"], dtype=torch.float64, device="cuda").reshape(B, 2).clone()
+        hx = torch.full((B, T + 1, 6), float("nan"), dtype=torch.float64, device="cuda")
+        hu = torch.full((B, T, 2), float("nan"), dtype=torch.float64, device="cuda")
+        hx[:, 0] = x
+        st = torch.empty((T, B), dtype=torch.int32, device="cuda")
+        it = torch.empty((T, B), dtype=torch.int32, device="cuda")
+        pol = np.zeros((T, B), dtype=bool)
+        for t in range(T):
+            # (the step entry point on the loop's state: the loop applies exactly its u_cmd -- it tells which steps polished)
+            prt = TB.ref_window_batch(paths, x[:, 0].cpu().numpy(), vr.cpu().numpy(), N, Ts).cpu().numpy()
+            g = TB.mpc_step_batch(x.cpu().numpy(), u.cpu().numpy(), prt, vr.cpu().numpy(), cfg)
+            pol[t] = g["polished"].cpu().numpy() > 0
+            TB.closed_loop_step(x, u, paths, vr, cfg, None, t, hx, hu, st[t], it[t])
+            assert torch.equal(hx[:, t + 1], x) and torch.equal(hu[:, t], u), (name, t)
+            assert torch.equal(g["u_cmd"], hu[:, t]), (name, t)
+        runs[name] = dict(X=hx.cpu().numpy(), U=hu.cpu().numpy(), S=st.cpu().numpy(), I=it.cpu().numpy(), pol=pol)
+    a, b = runs["bounded"], runs["none"]
+    assert np.array_equal(a["S"], b["S"]), (a["S"], b["S"])
+    bar = np.zeros(B)   # per instance: the loosest bar of the commands so far
+    for t in range(T):
+        ok = a["S"][t] <= 1
+        both, neither = a["pol"][t] & b["pol"][t] & ok, ~a["pol"][t] & ~b["pol"][t] & ok & (a["I"][t] == b["I"][t])
+        du = np.abs(a["U"][:, t] - b["U"][:, t]).max(axis=1)
+        dx = np.abs(a["X"][:, t + 1] - b["X"][:, t + 1]).max(axis=1)
+        print(f"small horizon, both tiers, step {t}: du {du} dx {dx} polished {a['pol'][t]} {b['pol'][t]} "
+              f"iters {a['I'][t]} {b['I'][t]}")
+        assert du[both].max(initial=0.0) <= 1e-6 and du[neither].max(initial=0.0) <= 1e-4, (t, du)
+        assert (both | neither | ~ok).all(), (t, a["pol"][t], b["pol"][t], a["I"][t], b["I"][t])
+        # (not ok: both runs keep their u_prev, the statuses being equal -- as far apart as the commands before)
+        assert (du[~ok] <= bar[~ok]).all(), (t, du, bar)
+        bar = np.maximum(bar, np.where(neither, 1e-4, 1e-6))
+        assert (dx <= bar).all(), (t, dx, bar)
+
+
 # ------------------------------------------------------------------ dataset emitter (f1)
 
 def test_dataset_generate_single_rank(gpu, oracle_lib, tmp_path):

@@ -42,6 +42,17 @@ def test_mpc_route_under_asan_ubsan(tmp_path):
     assert "san_route ok" in r.stdout and "ERROR" not in r.stderr
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_mpc_queue_under_asan_ubsan(tmp_path):
+    """csrc/mpc_queue.h (the fused closed loop's work-queue order, integers only) alone under g++: decode is a
+    bijection onto (step, rank), encode inverts it, levels never decrease, and every instance's steps stay in
+    increasing queue order, over 816 settings of B, nsteps and the lead set."""
+    exe = str(tmp_path / "san_queue")
+    _run(["g++", *SAN, "-std=c++17", "-Wall", "-Werror", "-o", exe, os.path.join(HERE, "sanitize", "san_queue.cpp")])
+    r = _run([exe], env=ENV)
+    assert "san_queue ok" in r.stdout and "ERROR" not in r.stderr
+
+
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_oracle_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "san_oracle")

@@ -808,6 +808,8 @@ __global__ __launch_bounds__(GEN_NT) void solve_gen_kernel(const KArgs a, double
     __syncthreads();
 
     // ---- outputs (orc_mpc_step_warm): U, X by the linear model, objective, u_cmd ----
+    // (its own output stage, not mpc_frame.h's: the objective is summed serially on one thread with lateral_error over a
+    // state-major X, so its bits differ from the condensed kernels' block sum by construction)
     const bool good = inputs_ok && (status == TRAJ_STATUS_OPTIMAL || status == TRAJ_STATUS_OPTIMAL_INACCURATE);
     const double nan = __builtin_nan("");
     double* U = w.U;

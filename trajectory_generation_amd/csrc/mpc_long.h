@@ -24,6 +24,8 @@
 // LDS buffers.
 #pragma once
 #include "mpc_common.h"
+#include "mpc_frame.h"
+#include "mpc_osqp_rules.h"
 #include "mpc_sizes.h"   // long_ld, long_ws_doubles, LONG_NKL
 
 namespace tgmpc {
@@ -50,7 +52,6 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
     // plant update at the end, so every read goes through these copies
     __shared__ double s_xc[CLOSED ? 6 : 1], s_uc[CLOSED ? 2 : 1], s_prc[CLOSED ? 3 * (NT / 2 + 1) : 1];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const traj_vehicle_params& p = a.p;
     const traj_mpc_config& c = a.c;
     const int N = c.N, n = 2 * N, ld = long_ld(n);
     const bool own = t < n;
@@ -104,26 +105,9 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
     };
     const double* vr = a.vref + (size_t)(N + 1) * b;
     if constexpr (CLOSED) {
-        if (t < 6) s_xc[t] = a.x_state[6 * (size_t)b + t];
-        if (t < 2) s_uc[t] = a.u_state[2 * (size_t)b + t];
+        load_state<true, false>(a, b, t, s_xc, s_uc);
         __syncthreads();
-        // main.py:51-68: xs_0 = X, xs_{k+1} = xs_k + vref_k Ts (serial, as ref_window_kernel / mpc_solve.h); ys = path(xs),
-        // phi* = atan(path'(xs))
-        if (t == 0) {
-            double xs = s_xc[0];
-            s_prc[0] = xs;
-            for (int k = 0; k < N; ++k) {
-                xs = xs + vr[k] * c.Ts;
-                s_prc[3 * (k + 1)] = xs;
-            }
-        }
-        __syncthreads();
-        for (int k = t; k <= N; k += NT) {
-            double y, dy;
-            path_eval(a.path, b, s_prc[3 * k], y, dy);
-            s_prc[3 * k + 1] = y;
-            s_prc[3 * k + 2] = pm_atan(dy);
-        }
+        build_window(a, b, N, c.Ts, s_xc, vr, s_prc, t, NT);
         __syncthreads();
     }
     const double* x0 = CLOSED ? s_xc : a.x0 + 6 * (size_t)b;
@@ -346,12 +330,6 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
             const double* vb = bcast(v);
             return own ? row_dot(Kat, vb) : 0.0;
         };
-        auto rho_for = [&](double l, double u, double rho) -> double {
-            if (l <= -INFTY * MIN_SCALING && u >= INFTY * MIN_SCALING) return RHO_MIN;
-            if (u - l < RHO_TOL) return RHO_EQ_OVER_INEQ * rho;
-            return rho;
-        };
-        struct Res { double pr, dr, eps_p, eps_d, prs, drs, pn, dn; };
         auto residuals = [&](double x, double zb, double zr, double yb, double yr) -> Res {
             const double px = Pmul(x);
             double axb, axr;
@@ -443,7 +421,7 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
             __syncthreads();
             if (!ok) {
                 if (phase == PH_ADMM) { status = TRAJ_STATUS_SOLVER_ERROR; break; }
-                if (c.polish_mode == 1 && rounds < c.polish_max_rounds && iter < c.max_iter) {
+                if (c.polish_mode == 1 && polish_continues(c, rounds, iter)) {
                     ++rounds;
                     escale *= 1e-2;
                     ++iter;
@@ -478,9 +456,8 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
                         r = residuals(x, zb, zr, yb, yr);
                         if (r.pr <= escale * r.eps_p && r.dr <= escale * r.eps_d) { converged = true; break; }
                         if (c.adaptive_rho) {
-                            double est = rho * sqrt((r.prs / (r.pn + DIV_TOL)) / (r.drs / (r.dn + DIV_TOL) + DIV_TOL));
-                            est = fmin(fmax(est, RHO_MIN), RHO_MAX);
-                            if (est > rho * c.adaptive_rho_tol || est < rho / c.adaptive_rho_tol) {
+                            const double est = rho_estimate(rho, r);
+                            if (needs_refactor(est, rho, c.adaptive_rho_tol)) {
                                 rho = est;
                                 rb = rho_for(slb, sub, rho);
                                 rr = rho_for(slr, sur, rho);
@@ -496,14 +473,11 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
                 else {
                     iter = c.max_iter;
                     r = residuals(x, zb, zr, yb, yr);
-                    status = (rounds > 0 && r.pr <= r.eps_p && r.dr <= r.eps_d) ? TRAJ_STATUS_OPTIMAL
-                             : (r.pr <= 10.0 * r.eps_p && r.dr <= 10.0 * r.eps_d) ? TRAJ_STATUS_OPTIMAL_INACCURATE
-                                                                                 : TRAJ_STATUS_USER_LIMIT;
+                    status = status_at_cap(rounds, r);
                 }
                 if (status == TRAJ_STATUS_OPTIMAL && c.polish) {
-                    // OSQP active sets: lower if z - l < -y, upper if u - z < y
-                    actb = own ? ((zb - slb < -yb) ? -1 : ((sub - zb < yb) ? 1 : 0)) : 0;
-                    actr = own ? ((zr - slr < -yr) ? -1 : ((sur - zr < yr) ? 1 : 0)) : 0;
+                    actb = own ? active_sign(zb, slb, sub, yb) : 0;
+                    actr = own ? active_sign(zr, slr, sur, yr) : 0;
                     ps = 1;
                     phase = PH_POLISH;
                 } else {
@@ -588,12 +562,12 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
                 }
                 if (ps < c.polish_max_pass) {
                     // primal-dual active-set update with the OSQP rule on the polished (Ax, y)
-                    actb = own ? ((axb - slb < -pyb) ? -1 : ((sub - axb < pyb) ? 1 : 0)) : 0;
-                    actr = own ? ((axr - slr < -pyr) ? -1 : ((sur - axr < pyr) ? 1 : 0)) : 0;
+                    actb = own ? active_sign(axb, slb, sub, pyb) : 0;
+                    actr = own ? active_sign(axr, slr, sur, pyr) : 0;
                     ++ps;
                     continue;
                 }
-                if (rounds < c.polish_max_rounds && iter < c.max_iter) {
+                if (polish_continues(c, rounds, iter)) {
                     // not certified: continue ADMM to a 100x tighter tolerance, then polish again
                     ++rounds;
                     escale *= 1e-2;
@@ -606,24 +580,16 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
         }
         if (iter > c.max_iter) iter = c.max_iter;
         xsol = D * x;
-        if (CLOSED && a.wsWarm && t == 0) {
-            double* wv = a.wsWarm + 4 * (size_t)b;
-            wv[0] = rho;
-            wv[1] = (status == TRAJ_STATUS_OPTIMAL || status == TRAJ_STATUS_OPTIMAL_INACCURATE) ? 1.0 : 0.0;
-            wv[2] = (double)iter;
-        }
+        if (CLOSED && a.wsWarm && t == 0)
+            store_warm<false>(a, b, rho, status == TRAJ_STATUS_OPTIMAL || status == TRAJ_STATUS_OPTIMAL_INACCURATE, iter);
     } else {
         status = early;
         iter = 0;
-        if (CLOSED && a.wsWarm && t == 0) {
-            a.wsWarm[4 * (size_t)b + 1] = 0.0;
-            a.wsWarm[4 * (size_t)b + 2] = 0.0;
-        }
+        if (CLOSED && a.wsWarm && t == 0) store_warm_early<false>(a, b);
     }
 
     // ---- outputs (:257-275): U, X_opt by the linear model, the objective, u_cmd ----
     const bool good = (status == TRAJ_STATUS_OPTIMAL || status == TRAJ_STATUS_OPTIMAL_INACCURATE);
-    const double nan = __builtin_nan("");
     double* const Ub = s_bc[0];
     __syncthreads();
     Ub[t] = own ? xsol : 0.0;
@@ -632,72 +598,21 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
     if constexpr (CLOSED) {
         // plant x <- x + Ts f(x, u_cmd) (main.py:97), u_prev <- u_cmd (:101); the history and this step's outcome
         // (main.py:94 keeps only u_cmd: no X_opt, no objective)
-        if (t == 0) {
-            const double uc0 = good ? Ub[0] : up[0], uc1 = good ? Ub[1] : up[1];
-            double xs[6], f[6], u[2] = {uc0, uc1};
-            for (int i = 0; i < 6; ++i) xs[i] = x0[i];
-            f_cont(p, xs, u, f);
-            for (int i = 0; i < 6; ++i) {
-                const double xn = xs[i] + c.Ts * f[i];
-                a.x_state[6 * (size_t)b + i] = xn;
-                if (a.hist_x) a.hist_x[((size_t)b * (a.hist_T + 1) + a.t + 1) * 6 + i] = xn;
-            }
-            a.u_state[2 * (size_t)b] = uc0;
-            a.u_state[2 * (size_t)b + 1] = uc1;
-            if (a.hist_u) {
-                a.hist_u[((size_t)b * a.hist_T + a.t) * 2] = uc0;
-                a.hist_u[((size_t)b * a.hist_T + a.t) * 2 + 1] = uc1;
-            }
-            if (a.status) a.status[b] = status;
-            if (a.iters) a.iters[b] = iter;
-        }
+        if (t == 0) plant_step<false>(a, b, 0, a.t, x0, good ? Ub[0] : up[0], good ? Ub[1] : up[1], status, iter);
         return;
     }
     // X_{k+1} = A_k X_k + B_k U_k + g_k, stage by stage (thread r < 6: state r); X in s_ex (6 (N+1) <= 4 NT)
     double* const Xs = &s_ex[0][0];
-    if (t < 6) Xs[t] = x0[t];
-    __syncthreads();
-    for (int k = 0; k < N; ++k) {
-        if (t < 6) {
-            double v = 0.0;
-            for (int cc = 0; cc < 6; ++cc) v += gA[k * 36 + t * 6 + cc] * Xs[6 * k + cc];
-            v += gB[k * 12 + t * 2] * Ub[2 * k] + gB[k * 12 + t * 2 + 1] * Ub[2 * k + 1] + gg[6 * k + t];
-            Xs[6 * (k + 1) + t] = v;
-        }
-        __syncthreads();
-    }
+    rollout_xopt(gA, gB, gg, 36, 12, 6, N, Ub, x0, Xs, t);
     double op = 0.0;
     for (int k = t; k <= N; k += NT) {
-        const double* X = Xs + 6 * k;
         double s, co;
         pm_sincos(pref[3 * k + 2], &s, &co);
-        const double ec = s * (X[0] - pref[3 * k]) - co * (X[1] - pref[3 * k + 1]);
-        const double ep = X[2] - pref[3 * k + 2];
-        const double ev = X[3] - vr[k];
-        op += c.q_c * ec * ec + c.q_phi * ep * ep + c.q_vx * ev * ev;
-        if (k < N) {
-            const double u0 = Ub[2 * k], u1 = Ub[2 * k + 1];
-            const double d0 = u0 - (k == 0 ? up[0] : Ub[2 * k - 2]);
-            const double d1 = u1 - (k == 0 ? up[1] : Ub[2 * k - 1]);
-            op += u0 * (c.R[0] * u0 + c.R[1] * u1) + u1 * (c.R[2] * u0 + c.R[3] * u1);
-            op += d0 * (c.Rd[0] * d0 + c.Rd[1] * d1) + d1 * (c.Rd[2] * d0 + c.Rd[3] * d1);
-        }
+        stage_cost(c, k, N, Xs, pref, vr[k], s, co, Ub, up, op);
     }
     const double obj = block_sum(op);
-    if (t == 0) {
-        a.u_cmd[2 * b] = good ? Ub[0] : up[0];
-        a.u_cmd[2 * b + 1] = good ? Ub[1] : up[1];
-        a.status[b] = status;
-        if (a.objective) a.objective[b] = good ? obj : nan;
-        if (a.iters) a.iters[b] = iter;
-        if (a.polished) a.polished[b] = pol;
-    }
-    if (a.U_opt && own) a.U_opt[(size_t)b * 2 * N + ch * N + kk] = good ? xsol : nan;
-    if (a.X_opt)
-        for (int i = t; i < 6 * (N + 1); i += NT) {
-            const int rr = i / (N + 1), k = i % (N + 1);
-            a.X_opt[(size_t)b * 6 * (N + 1) + i] = good ? Xs[6 * k + rr] : nan;
-        }
+    store_outputs(a, b, N, t, NT, good, good ? Ub[0] : up[0], good ? Ub[1] : up[1], status, obj, iter, pol, own, ch, kk,
+                  xsol, Xs);
 }
 
 }  // namespace tgmpc

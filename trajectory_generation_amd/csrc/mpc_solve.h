@@ -17,7 +17,10 @@
 // Everything is float64, like the reference.
 #pragma once
 #include "mpc_common.h"
+#include "mpc_frame.h"
 #include "mpc_linearize.h"
+#include "mpc_osqp_rules.h"
+#include "mpc_queue.h"
 
 #ifndef TGMPC_PRIO_ITERS
 #define TGMPC_PRIO_ITERS 100   // fused run: ADMM iterations after which a solve's wave takes issue priority
@@ -233,37 +236,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     long long* const dbg_items = DIAG ? a.dbg_items : nullptr;
     int b = (CLOSED && a.perm) ? a.perm[blockIdx.x] : (int)blockIdx.x;
     if constexpr (FUSED) {
-        // item q <-> (step, rank).  Plain order: all ranks of step 0, then of step 1, ...  With a lead
-        // (a.lead_steps > 0, heavy = ranks < a.lead_h, the instances with the most ADMM iterations in the
-        // previous launch): the heavy instances' first lead steps come first, then level s holds the heavy
-        // instances' step s + lead followed by the light instances' step s -- the long chains are not held
-        // back by the level front.  Every instance's steps stay in increasing queue order, so an item only
-        // ever waits for an item drawn before it: no deadlock.
-        const int Bq = a.B, S = a.nsteps;
-        const int L = (a.lead_h > 0) ? min(a.lead_steps, S) : 0, H = (L > 0) ? a.lead_h : 0;
-        const int P = L * H, full = (S - L) * Bq;
-        auto decode = [&](int q, int& st, int& rk) -> int {   // returns the queue level of q
-            if (q < P) {
-                st = q / H;
-                rk = q - st * H;
-                return 0;
-            }
-            const int q1 = q - P;
-            if (q1 < full) {
-                const int lv = q1 / Bq;
-                rk = q1 - lv * Bq;
-                st = (rk < H) ? lv + L : lv;
-                return lv;
-            }
-            const int q2 = q1 - full, lv = (S - L) + q2 / (Bq - H);
-            rk = H + (q2 - (lv - (S - L)) * (Bq - H));
-            st = lv;
-            return lv;
-        };
-        auto encode = [&](int st, int rk) -> int {
-            if (rk < H) return (st < L) ? st * H + rk : P + (st - L) * Bq + rk;
-            return (st < S - L) ? P + st * Bq + rk : P + full + (st - (S - L)) * (Bq - H) + (rk - H);
-        };
+        const QueueOrder qo(a.B, a.nsteps, a.lead_steps, a.lead_h);   // item q <-> (step, rank): mpc_queue.h
         // Run-ahead (a.run_ahead > 0): the workgroup that completed (step - 1, rank) claims the instance's next
         // step itself while that step is at most run_ahead levels past the draw front -- an instance whose steps
         // are cheap runs ahead of the level order, so a long chain (a solve at the iteration cap late in the
@@ -273,17 +246,17 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         // waits, if it must, only for the claim of (s - 1, b), whose queue item was drawn before its own.
         __syncthreads();
         if (threadIdx.x == 0) {
-            int* const claim = a.queue + 2 + Bq;
-            const int total = Bq * S;
+            int* const claim = a.queue + 2 + qo.Bq;
+            const int total = qo.total();
             int got = -1;
-            if (a.run_ahead > 0 && ra_step > 0 && ra_step < S) {
+            if (a.run_ahead > 0 && ra_step > 0 && ra_step < qo.S) {
                 int fs, fr;
                 const int front = __hip_atomic_load(&a.queue[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int flv = (front < total) ? decode(front, fs, fr) : S;
-                const int rlv = (ra_rank < H) ? max(ra_step - L, 0) : ra_step;   // the level of (ra_step, ra_rank)
+                const int flv = (front < total) ? qo.decode(front, fs, fr) : qo.S;
+                const int rlv = qo.level_of(ra_step, ra_rank);
                 const int rb = a.perm ? a.perm[ra_rank] : ra_rank;
                 if (rlv <= flv + a.run_ahead && atomicCAS(&claim[rb], ra_step, ra_step + 1) == ra_step) {
-                    got = encode(ra_step, ra_rank);
+                    got = qo.encode(ra_step, ra_rank);
                     if (dbg_items) dbg_items[4 * (size_t)got] = __builtin_amdgcn_s_memrealtime();
                 }
             }
@@ -293,7 +266,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 const long long t_draw = __builtin_amdgcn_s_memrealtime();
                 if (a.run_ahead <= 0) { got = q; }
                 int qs, qr;
-                decode(q, qs, qr);
+                qo.decode(q, qs, qr);
                 const int qb = a.perm ? a.perm[qr] : qr;
                 int spins = 0;
                 for (; got < 0;) {
@@ -318,7 +291,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         const int q = s_item;
         if (q >= a.B * a.nsteps) break;
         int rank;
-        decode(q, step, rank);
+        qo.decode(q, step, rank);
         ra_step = step + 1;
         ra_rank = rank;
         item_of_wave = q;
@@ -452,37 +425,13 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // register loops over the full capacity NN rely on
     for (int i = t; i < NEX; i += NT) s_ex[i] = 0.0;
     for (int i = t; i < NFS; i += NT) s_F[i] = 0.0;
-    if (FUSED) {   // the state the instance's previous step published (sc1, see st_coh)
-        if (t < 6) s_x0[t] = ld_coh(a.x_state + 6 * b + t);
-        if (t < 2) s_up[t] = ld_coh(a.u_state + 2 * b + t);
-    } else if (CLOSED) {
-        if (t < 6) s_x0[t] = a.x_state[6 * b + t];
-        if (t < 2) s_up[t] = a.u_state[2 * b + t];
-    } else {
-        if (t < 6) s_x0[t] = a.x0[6 * b + t];
-        if (t < 2) s_up[t] = a.u_prev[2 * b + t];
-    }
+    load_state<CLOSED, FUSED>(a, b, t, s_x0, s_up);
     for (int i = t; i < N + 1; i += NT) s_vref[i] = a.vref[(size_t)(N + 1) * b + i];
     if (!CLOSED)
         for (int i = t; i < 3 * (N + 1); i += NT) s_pref[i] = a.path_ref[(size_t)3 * (N + 1) * b + i];
     __syncthreads();
     if (CLOSED) {
-        // MPC/main.py:51-68: xs_0 = X, xs_{k+1} = xs_k + vref_k Ts; ys = path(xs); phi* = atan(path'(xs))
-        if (t == 0) {
-            double xs = s_x0[0];
-            s_pref[0] = xs;
-            for (int k = 0; k < N; ++k) {
-                xs = xs + s_vref[k] * Ts;
-                s_pref[3 * (k + 1)] = xs;
-            }
-        }
-        __syncthreads();
-        for (int k = t; k <= N; k += NT) {
-            double y, dy;
-            path_eval(a.path, b, s_pref[3 * k], y, dy);
-            s_pref[3 * k + 1] = y;
-            s_pref[3 * k + 2] = pm_atan(dy);
-        }
+        build_window(a, b, N, Ts, s_x0, s_vref, s_pref, t, NT);
         __syncthreads();
     }
     {
@@ -1084,15 +1033,8 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
             asm volatile("" : "+v"(r));
             return own ? r : 0.0;
         };
-        auto rho_for = [&](double l, double u, double rho) -> double {
-            if (l <= -INFTY * MIN_SCALING && u >= INFTY * MIN_SCALING) return RHO_MIN;
-            if (u - l < RHO_TOL) return RHO_EQ_OVER_INEQ * rho;
-            return rho;
-        };
-        // residuals (OSQP update_info, unscaled norms; compute_rho_estimate's scaled norms).  Norms that only
-        // ever enter as a max of several are combined in the lane first, so 8 maxima cross the wave:
-        //   pr, max(|Ax|, |z|), dr, max(|Px|, |A'y|, |q|) (unscaled); prs, drs, pn, dn (scaled)
-        struct Res { double pr, dr, eps_p, eps_d, prs, drs, pn, dn; };
+        // residuals (Res of mpc_osqp_rules.h).  Norms that only ever enter as a max of several are combined in the
+        // lane first, so 8 maxima cross the wave
         auto residuals = [&](double x, double zb, double zr, double yb, double yr) -> Res {
             double px = Pmul(x);   // (first: its temporaries then coexist with no other)
             double axb, axr;
@@ -1638,7 +1580,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 if (phase == PH_ADMM) { status = TRAJ_STATUS_SOLVER_ERROR; break; }
                 // failed reduced-KKT factorization = unsuccessful polish (polish.c): the ADMM
                 // solution and status stand; exact mode continues ADMM like an uncertified pass
-                if (c.polish_mode == 1 && rounds < c.polish_max_rounds && iter < c.max_iter) {
+                if (c.polish_mode == 1 && polish_continues(c, rounds, iter)) {
                     ++rounds;
                     escale *= 1e-2;
                     ++iter;
@@ -1688,9 +1630,8 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                         ++n_res;
                         if (r.pr <= escale * r.eps_p && r.dr <= escale * r.eps_d) { converged = true; break; }
                         if (c.adaptive_rho) {
-                            double est = rho * sqrt((r.prs / (r.pn + DIV_TOL)) / (r.drs / (r.dn + DIV_TOL) + DIV_TOL));
-                            est = fmin(fmax(est, RHO_MIN), RHO_MAX);
-                            if (est > rho * c.adaptive_rho_tol || est < rho / c.adaptive_rho_tol) {
+                            const double est = rho_estimate(rho, r);
+                            if (needs_refactor(est, rho, c.adaptive_rho_tol)) {
                                 rho = uniformize(est);
                                 rho_rows();
                                 refactor = true;
@@ -1705,17 +1646,12 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 else {
                     iter = c.max_iter;
                     r = residuals(x, zb, zr, yb, yr);
-                    // an exact-mode continuation round that runs out of iterations still meets eps
-                    status = (rounds > 0 && r.pr <= r.eps_p && r.dr <= r.eps_d) ? TRAJ_STATUS_OPTIMAL
-                             : (r.pr <= 10.0 * r.eps_p && r.dr <= 10.0 * r.eps_d) ? TRAJ_STATUS_OPTIMAL_INACCURATE
-                                                                                 : TRAJ_STATUS_USER_LIMIT;
+                    status = status_at_cap(rounds, r);
                 }
                 if (status == TRAJ_STATUS_OPTIMAL && c.polish) {
-                    // OSQP active sets: lower if z - l < -y, upper if u - z < y
                     const dpair bb = pair(P_BB), br = pair(P_BR);
-                    const double slb = bb.x, sub = bb.y, slr = br.x, sur = br.y;
-                    actb = own ? ((zb - slb < -yb) ? -1 : ((sub - zb < yb) ? 1 : 0)) : 0;
-                    actr = own ? ((zr - slr < -yr) ? -1 : ((sur - zr < yr) ? 1 : 0)) : 0;
+                    actb = own ? active_sign(zb, bb.x, bb.y, yb) : 0;
+                    actr = own ? active_sign(zr, br.x, br.y, yr) : 0;
                     ps = 1;
                     phase = PH_POLISH;
                 } else {
@@ -1816,12 +1752,12 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 }
                 if (ps < c.polish_max_pass) {
                     // primal-dual active-set update with the OSQP rule on the polished (Ax, y)
-                    actb = own ? ((axb - slb < -pyb) ? -1 : ((sub - axb < pyb) ? 1 : 0)) : 0;
-                    actr = own ? ((axr - slr < -pyr) ? -1 : ((sur - axr < pyr) ? 1 : 0)) : 0;
+                    actb = own ? active_sign(axb, slb, sub, pyb) : 0;
+                    actr = own ? active_sign(axr, slr, sur, pyr) : 0;
                     ++ps;
                     continue;
                 }
-                if (rounds < c.polish_max_rounds && iter < c.max_iter) {
+                if (polish_continues(c, rounds, iter)) {
                     // not certified: continue ADMM to a 100x tighter tolerance, then polish again
                     ++rounds;
                     escale *= 1e-2;
@@ -1834,15 +1770,8 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         }
         if (iter > c.max_iter) iter = c.max_iter;
         xsol = cold(C_D) * x;
-        if (CLOSED && a.wsWarm && t == 0) {
-            const bool okst = (status == TRAJ_STATUS_OPTIMAL || status == TRAJ_STATUS_OPTIMAL_INACCURATE);
-            double* wv = a.wsWarm + 4 * (size_t)b;
-            const double w[3] = {rho, okst ? 1.0 : 0.0, (double)(iter > c.max_iter ? c.max_iter : iter)};
-            for (int i = 0; i < 3; ++i) {
-                if (FUSED) st_coh(wv + i, w[i]);
-                else wv[i] = w[i];
-            }
-        }
+        if (CLOSED && a.wsWarm && t == 0)
+            store_warm<FUSED>(a, b, rho, status == TRAJ_STATUS_OPTIMAL || status == TRAJ_STATUS_OPTIMAL_INACCURATE, iter);
         if (pol_open) toc(cyc_pol);
         stamp(8, nfact);
         stamp(10, ps);
@@ -1853,15 +1782,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     } else {
         status = early;
         iter = 0;
-        if (CLOSED && a.wsWarm && t == 0) {
-            if (FUSED) {
-                st_coh(a.wsWarm + 4 * (size_t)b + 1, 0.0);
-                st_coh(a.wsWarm + 4 * (size_t)b + 2, 0.0);
-            } else {
-                a.wsWarm[4 * (size_t)b + 1] = 0.0;
-                a.wsWarm[4 * (size_t)b + 2] = 0.0;
-            }
-        }
+        if (CLOSED && a.wsWarm && t == 0) store_warm_early<FUSED>(a, b);
     }
 
     stamp(6, __builtin_amdgcn_s_memtime());
@@ -1874,72 +1795,20 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     __syncthreads();
     // X_opt by the linear model X_{k+1} = A_k X_k + B_k U_k + g_k (s_xh reused); the closed loop
     // returns neither X_opt nor the objective (main.py:94 keeps only u_cmd): skipped there
-    if (t < 6) s_xh[t] = s_x0[t];
-    __syncthreads();
-    for (int k = 0; k < (CLOSED ? 0 : N); ++k) {
-        if (t < 6) {
-            double v = 0.0;
-            for (int cc = 0; cc < 6; ++cc) v += gA[k * 36 + t * 6 + cc] * s_xh[6 * k + cc];
-            v += gB[k * 12 + t * 2] * Ubuf[2 * k] + gB[k * 12 + t * 2 + 1] * Ubuf[2 * k + 1] + gg[6 * k + t];
-            s_xh[6 * (k + 1) + t] = v;
-        }
-        __syncthreads();
-    }
+    rollout_xopt(gA, gB, gg, 36, 12, 6, CLOSED ? 0 : N, Ubuf, s_x0, s_xh, t);
     // objective = cost of :217-250 at (X_opt, U_opt)
     double op = 0.0;
-    for (int k = t; k <= (CLOSED ? -1 : N); k += NT) {
-        const double* X = s_xh + 6 * k;
-        double s = s_sc[2 * k], co = s_sc[2 * k + 1];
-        double ec = s * (X[0] - s_pref[3 * k]) - co * (X[1] - s_pref[3 * k + 1]);
-        double ep = X[2] - s_pref[3 * k + 2];
-        double ev = X[3] - s_vref[k];
-        op += c.q_c * ec * ec + c.q_phi * ep * ep + c.q_vx * ev * ev;
-        if (k < N) {
-            double u0 = Ubuf[2 * k], u1 = Ubuf[2 * k + 1];
-            double d0 = u0 - (k == 0 ? s_up[0] : Ubuf[2 * k - 2]);
-            double d1 = u1 - (k == 0 ? s_up[1] : Ubuf[2 * k - 1]);
-            op += u0 * (c.R[0] * u0 + c.R[1] * u1) + u1 * (c.R[2] * u0 + c.R[3] * u1);
-            op += d0 * (c.Rd[0] * d0 + c.Rd[1] * d1) + d1 * (c.Rd[2] * d0 + c.Rd[3] * d1);
-        }
-    }
+    for (int k = t; k <= (CLOSED ? -1 : N); k += NT)
+        stage_cost(c, k, N, s_xh, s_pref, s_vref[k], s_sc[2 * k], s_sc[2 * k + 1], Ubuf, s_up, op);
     double obj = CLOSED ? 0.0 : block_sum(op);
     stamp(7, __builtin_amdgcn_s_memtime());
     stamp(3, __builtin_amdgcn_s_memrealtime());
-    const double nan = __builtin_nan("");
     double uc0 = good ? Ubuf[0] : s_up[0], uc1 = good ? Ubuf[1] : s_up[1];
     if (CLOSED) {
         // plant x <- x + Ts f(x, u_cmd) (main.py:97), u_prev <- u_cmd (:101)
         if (t == 0) {
-            double xs[6], f[6], u[2] = {uc0, uc1};
-            for (int i = 0; i < 6; ++i) xs[i] = s_x0[i];
-            f_cont(p, xs, u, f);
-            for (int i = 0; i < 6; ++i) {
-                double xn = xs[i] + Ts * f[i];
-                if (FUSED) st_coh(a.x_state + 6 * b + i, xn);
-                else a.x_state[6 * b + i] = xn;
-                if (a.hist_x) a.hist_x[((size_t)b * (a.hist_T + 1) + tstep + 1) * 6 + i] = xn;
-            }
+            plant_step<FUSED>(a, b, step, tstep, s_x0, uc0, uc1, status, iter);
             if (FUSED) {
-                st_coh(a.u_state + 2 * b, uc0);
-                st_coh(a.u_state + 2 * b + 1, uc1);
-            } else {
-                a.u_state[2 * b] = uc0;
-                a.u_state[2 * b + 1] = uc1;
-            }
-
-            if (a.hist_u) {
-                a.hist_u[((size_t)b * a.hist_T + tstep) * 2] = uc0;
-                a.hist_u[((size_t)b * a.hist_T + tstep) * 2 + 1] = uc1;
-            }
-            if (a.status) a.status[(size_t)step * a.B + b] = status;
-            if (a.iters) a.iters[(size_t)step * a.B + b] = iter;
-            if (FUSED) {
-                // mean iterations per step of this launch (the next launch's order), accumulated
-                if (a.wsWarm) {
-                    double* m = a.wsWarm + 4 * (size_t)b + 3;
-                    const double acc = (step == 0 ? 0.0 : ld_coh(m)) + iter;
-                    st_coh(m, (step == a.nsteps - 1) ? acc / a.nsteps : acc);
-                }
                 if (step == a.nsteps - 1) stamp(23, __builtin_amdgcn_s_memrealtime());   // launch span
                 if (dbg_items) dbg_items[4 * (size_t)item_of_wave + 2] = __builtin_amdgcn_s_memrealtime();
                 // hand the instance to whichever workgroup takes its next step: the sc1 state stores
@@ -1951,21 +1820,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         __syncthreads();
         continue;
     }
-    if (t == 0) {
-        a.u_cmd[2 * b] = uc0;
-        a.u_cmd[2 * b + 1] = uc1;
-        a.status[b] = status;
-        if (a.objective) a.objective[b] = good ? obj : nan;
-        if (a.iters) a.iters[b] = iter;
-        if (a.polished) a.polished[b] = pol;
-    }
-    if (a.U_opt && own) a.U_opt[(size_t)b * 2 * N + ch * N + kk] = good ? xsol : nan;
-    if (a.X_opt) {
-        for (int i = t; i < 6 * (N + 1); i += NT) {
-            int r = i / (N + 1), k = i % (N + 1);
-            a.X_opt[(size_t)b * 6 * (N + 1) + i] = good ? s_xh[6 * k + r] : nan;
-        }
-    }
+    store_outputs(a, b, N, t, NT, good, uc0, uc1, status, obj, iter, pol, own, ch, kk, xsol, s_xh);
     }   // steps / work items
 }
 

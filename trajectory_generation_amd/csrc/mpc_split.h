@@ -24,6 +24,7 @@
 // polish only.  CLOSED: as mpc_long.h (window from the state, warm rho, plant update, history).
 #pragma once
 #include "mpc_common.h"
+#include "mpc_frame.h"
 #include "mpc_linearize.h"
 #include "mpc_sizes.h"   // split_h, split_ws_doubles
 
@@ -70,6 +71,10 @@ __device__ __forceinline__ double pair_max(double v) {   // NaN-propagating
 // The sweep takes 2 pivots per round (one LDS round and one barrier per pair).  A 4-pivot form (a per-lane LDL' solve of
 // the block) measured 1.34-1.37 M against 1.42 M at config 3 and moved one capped instance's status in
 // test_config3_iteration_cap_steps_vs_oracle; it is not kept
+// Of mpc_frame.h this kernel calls the open-loop outputs only.  Its closed-loop frame (queue decode, hand-off, state and
+// window, OSQP rules, warm record, plant step) is its own text: the fused instances run at 256 VGPRs with spills, and
+// every variant of those parts as calls ran config 3 0.4 to 1.1 % slower or grew an instance's scratch
+// (profiles/mpc_frame_bench.json); the closed-loop instances are byte-equal to the code before the frame existed.
 // DIAG (fused only, when a diagnostic buffer is set: traj_debug_set_stamps): per-phase s_memtime stamps of each
 // instance's last step in a.dbg[b][0..11] (tools/split_phase.py); the production instances compile none of it.
 template <int H, bool CLOSED = false, bool FUSED = false, bool INLIN = FUSED, bool DIAG = false>
@@ -1065,7 +1070,6 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
 
     // ---- outputs (:257-275): U, X_opt by the linear model, the objective, u_cmd (CLOSED: the plant update) ----
     const bool good = (status == TRAJ_STATUS_OPTIMAL || status == TRAJ_STATUS_OPTIMAL_INACCURATE);
-    const double nan = __builtin_nan("");
     double* const Ub = s_bc[0];
     __syncthreads();
     if (h == 0) Ub[r] = own ? xsol : 0.0;
@@ -1116,54 +1120,18 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
     }
     // X_{k+1} = A_k X_k + B_k U_k + g_k, stage by stage (thread i < 6: state i)
     double* const Xs = s_xs;
-    if (t < 6) Xs[t] = x0[t];
-    __syncthreads();
-    for (int k = 0; k < N; ++k) {
-        if (t < 6) {
-            double v = 0.0;
-            for (int cc = 0; cc < 6; ++cc) v += gA[RA * k + t * 6 + cc] * Xs[6 * k + cc];
-            v += gB[RB * k + t * 2] * Ub[2 * k] + gB[RB * k + t * 2 + 1] * Ub[2 * k + 1] + gg[RG * k + t];
-            Xs[6 * (k + 1) + t] = v;
-        }
-        __syncthreads();
-    }
+    rollout_xopt(gA, gB, gg, RA, RB, RG, N, Ub, x0, Xs, t);
     // objective: the cost of :217-250 at (X_opt, U_opt), k = t over the threads, summed in a fixed order
     double op = 0.0;
-    for (int k = t; k <= N; k += NT) {
-        const double* X = Xs + 6 * k;
-        const double s = s_sc[k][0], co = s_sc[k][1];
-        const double ec = s * (X[0] - pref[3 * k]) - co * (X[1] - pref[3 * k + 1]);
-        const double ep = X[2] - pref[3 * k + 2];
-        const double ev = X[3] - s_vr[k];
-        op += c.q_c * ec * ec + c.q_phi * ep * ep + c.q_vx * ev * ev;
-        if (k < N) {
-            const double u0 = Ub[2 * k], u1 = Ub[2 * k + 1];
-            const double d0 = u0 - (k == 0 ? up[0] : Ub[2 * k - 2]);
-            const double d1 = u1 - (k == 0 ? up[1] : Ub[2 * k - 1]);
-            op += u0 * (c.R[0] * u0 + c.R[1] * u1) + u1 * (c.R[2] * u0 + c.R[3] * u1);
-            op += d0 * (c.Rd[0] * d0 + c.Rd[1] * d1) + d1 * (c.Rd[2] * d0 + c.Rd[3] * d1);
-        }
-    }
+    for (int k = t; k <= N; k += NT) stage_cost(c, k, N, Xs, pref, s_vr[k], s_sc[k][0], s_sc[k][1], Ub, up, op);
     // (every thread's partial -- not only half 0's rows: block_sum takes half-0 lanes, so sum by thread here)
     op = wave_sum_dpp(op);
     if (lane == 0) s_red[wid * 8] = op;
     __syncthreads();
     double obj = 0.0;
     for (int w = 0; w < WAVES; ++w) obj += s_red[w * 8];
-    if (t == 0) {
-        a.u_cmd[2 * b] = good ? Ub[0] : up[0];
-        a.u_cmd[2 * b + 1] = good ? Ub[1] : up[1];
-        a.status[b] = status;
-        if (a.objective) a.objective[b] = good ? obj : nan;
-        if (a.iters) a.iters[b] = iter;
-        if (a.polished) a.polished[b] = pol;
-    }
-    if (a.U_opt && own && h == 0) a.U_opt[(size_t)b * 2 * N + ch * N + kk] = good ? xsol : nan;
-    if (a.X_opt)
-        for (int i = t; i < 6 * (N + 1); i += NT) {
-            const int rr = i / (N + 1), k = i % (N + 1);
-            a.X_opt[(size_t)b * 6 * (N + 1) + i] = good ? Xs[6 * k + rr] : nan;
-        }
+    store_outputs(a, b, N, t, NT, good, good ? Ub[0] : up[0], good ? Ub[1] : up[1], status, obj, iter, pol, own && h == 0,
+                  ch, kk, xsol, Xs);
     }   // work items
 }
 

@@ -12,6 +12,7 @@
 
 #include "../../include/trajmpc.h"
 #include "mpc_common.h"
+#include "mpc_frame.h"
 #include "mpc_general.h"
 #include "mpc_long.h"
 #include "mpc_split.h"   // (the kernels are instantiated in split_inst.hip)
@@ -632,20 +633,8 @@ static int closed_step_long(const KArgs& a, const Route& r, void* ws, hipStream_
 __global__ void closed_sb_plant_kernel(const KArgs a, const double* u_cmd) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.B) return;
-    double xs[6], f[6], u[2] = {u_cmd[2 * (size_t)b], u_cmd[2 * (size_t)b + 1]};
-    for (int i = 0; i < 6; ++i) xs[i] = a.x_state[6 * (size_t)b + i];
-    f_cont(a.p, xs, u, f);
-    for (int i = 0; i < 6; ++i) {
-        const double xn = xs[i] + a.c.Ts * f[i];
-        a.x_state[6 * (size_t)b + i] = xn;
-        if (a.hist_x) a.hist_x[((size_t)b * (a.hist_T + 1) + a.t + 1) * 6 + i] = xn;
-    }
-    a.u_state[2 * (size_t)b] = u[0];
-    a.u_state[2 * (size_t)b + 1] = u[1];
-    if (a.hist_u) {
-        a.hist_u[((size_t)b * a.hist_T + a.t) * 2] = u[0];
-        a.hist_u[((size_t)b * a.hist_T + a.t) * 2 + 1] = u[1];
-    }
+    // (the status / iterations rows are the general solver's own: plant_update, not plant_step)
+    plant_update<false>(a, b, a.t, a.x_state + 6 * (size_t)b, u_cmd[2 * (size_t)b], u_cmd[2 * (size_t)b + 1]);
 }
 // (after the general solver's scratch in the workspace: the step's window [B, N+1, 3], u_cmd [B, 2], a status row [B])
 static int closed_step_sb(const KArgs& a0, const Route& r, void* ws, hipStream_t st) {
