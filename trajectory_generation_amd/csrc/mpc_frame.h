@@ -74,11 +74,10 @@ __device__ __forceinline__ void store_warm_early(const KArgs& a, int b) {
 
 // ---- plant update and step outcome ----
 // one thread: plant x <- x + Ts f(x, u_cmd) (main.py:97), u_prev <- u_cmd (:101), and the history rows of step tstep
+// (plant_publish: the stores, given f = f(x, u_cmd))
 template <bool FUSED>
-__device__ __forceinline__ void plant_update(const KArgs& a, int b, int tstep, const double* x0, double uc0, double uc1) {
-    double xs[6], f[6], u[2] = {uc0, uc1};
-    for (int i = 0; i < 6; ++i) xs[i] = x0[i];
-    f_cont(a.p, xs, u, f);
+__device__ __forceinline__ void plant_publish(const KArgs& a, int b, int tstep, const double* xs, const double* f,
+                                              double uc0, double uc1) {
     for (int i = 0; i < 6; ++i) {
         const double xn = xs[i] + a.c.Ts * f[i];
         if (FUSED) st_coh(a.x_state + 6 * (size_t)b + i, xn);
@@ -97,6 +96,41 @@ __device__ __forceinline__ void plant_update(const KArgs& a, int b, int tstep, c
         a.hist_u[((size_t)b * a.hist_T + tstep) * 2 + 1] = uc1;
     }
 }
+template <bool FUSED>
+__device__ __forceinline__ void plant_update(const KArgs& a, int b, int tstep, const double* x0, double uc0, double uc1) {
+    double xs[6], f[6], u[2] = {uc0, uc1};
+    for (int i = 0; i < 6; ++i) xs[i] = x0[i];
+    f_cont(a.p, xs, u, f);
+    plant_publish<FUSED>(a, b, tstep, xs, f, uc0, uc1);
+}
+// The same update where the item linearized in the workgroup (block_linearize's park): f(x_0, u_cmd) from what stage 0
+// of the rollout already evaluated at x_0.  park[0] = atan2(omega lf + vy, vx_eff) and park[1] = the rear Pacejka sine
+// sin(Cr atan(Br alpha_r)) do not depend on u; park[2], park[3] = sin / cos(phi_0).  They are the values tire_forces /
+// f_cont_sc form from the same x_0 (mpc_linearize.h, the rollout lanes' exact identities), so what is left is the front
+// slip at delta_cmd, Frx at d_cmd and sin / cos(delta_cmd).  The slip is tire_forces' "-atan2(...) + delta": the unary
+// minus of the parked atan2 (exact), then one add; every other expression is f_cont_sc's, term by term.
+template <bool FUSED>
+__device__ __forceinline__ void plant_update_parked(const KArgs& a, int b, int tstep, const double* x0, double uc0,
+                                                    double uc1, const double* park) {
+    const VP& p = a.p;
+    double xs[6], f[6];
+    for (int i = 0; i < 6; ++i) xs[i] = x0[i];
+    const double vx = xs[3], vy = xs[4], omega = xs[5];
+    const double at = park[0], sphi = park[2], cphi = park[3];
+    const double alpha_f = clampd(-at + uc1, -p.maxAlpha, p.maxAlpha);
+    const double Fy_f = p.Df * pm_tire_sin(p.Cf * pm_atan(p.Bf * alpha_f));
+    const double Fy_r = p.Dr * park[1];
+    const double Frx = (p.Cm1 - p.Cm2 * vx) * uc0 - p.Cr0 - p.Cr2 * (vx * vx);
+    double sd, cd;
+    pm_sincos(uc1, &sd, &cd);
+    f[0] = vx * cphi - vy * sphi;
+    f[1] = vx * sphi + vy * cphi;
+    f[2] = omega;
+    f[3] = (1.0 / p.m) * (Frx - Fy_f * sd + p.m * vy * omega);
+    f[4] = (1.0 / p.m) * (Fy_r + Fy_f * cd - p.m * vx * omega);
+    f[5] = (1.0 / p.Iz) * (Fy_f * p.lf * cd - Fy_r * p.lr);
+    plant_publish<FUSED>(a, b, tstep, xs, f, uc0, uc1);
+}
 // one thread: this step's status and iterations (row `step` of the launch), and, fused, the mean iterations per step of
 // this launch (the next launch's order), accumulated in the warm record
 template <bool FUSED>
@@ -111,11 +145,13 @@ __device__ __forceinline__ void step_outcome(const KArgs& a, int b, int step, in
         }
     }
 }
-// thread 0 at the end of a closed-loop step (fused: the caller's diagnostics stamps and the hand-off follow)
-template <bool FUSED>
+// thread 0 at the end of a closed-loop step (fused: the caller's diagnostics stamps and the hand-off follow); park: the
+// item's parked stage-0 values (PARK: plant_update_parked)
+template <bool FUSED, bool PARK = false>
 __device__ __forceinline__ void plant_step(const KArgs& a, int b, int step, int tstep, const double* x0, double uc0,
-                                           double uc1, int status, int iter) {
-    plant_update<FUSED>(a, b, tstep, x0, uc0, uc1);
+                                           double uc1, int status, int iter, const double* park = nullptr) {
+    if (PARK) plant_update_parked<FUSED>(a, b, tstep, x0, uc0, uc1, park);
+    else plant_update<FUSED>(a, b, tstep, x0, uc0, uc1);
     step_outcome<FUSED>(a, b, step, status, iter);
 }
 

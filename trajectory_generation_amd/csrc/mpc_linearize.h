@@ -258,28 +258,67 @@ __global__ __launch_bounds__(256) void jac_kernel(const KArgs a) {
 // Their sines go to tj[k][lane].  The phi pass (after the chain), lane v N + k: sincos(phi_k + {-0.0, +eps, -eps}),
 // v = 0 / 1 / 2: sin / cos(phi_k + 0.0) -> tj[k][21] / tj[k][2] (sin(phi + 0.0) = sin(phi) + 0.0 exactly, cos is
 // even), sin / cos(phi_k +- eps) -> tj[k][19 / 20] / tj[k][0 / 1], and lane k forms the rollout's f_0, f_1 of stage
-// k from the raw sin / cos.  An assembly pass (one stage per lane) then forms f at each perturbed point with f_parts
-// and the difference quotients: the values state_column / cheap_columns compute (jac_kernel), bit for bit.
+// k from the raw sin / cos.  An assembly pass then forms f at each perturbed point with f_parts and the difference
+// quotients: the values state_column / cheap_columns compute (jac_kernel), bit for bit.  Three lanes per stage, lane
+// 3 k + c: state column c (vx, vy, omega) and cheap column c (phi, d, delta) -- four f_parts per lane, the operands
+// picked by the role c; the lanes of a stage write their columns of A_k, B_k and then form two rows of g_k each.
+//
+// The sincos whose arguments are known before the chain are one lane-parallel call: lanes 0 / 1 / 2 take u1, u1 + eps,
+// u1 - eps (the chain's sin / cos(delta) and the delta column's), and, where the caller hands in its window (WIN; phis:
+// the N + 1 phi*_k, stride 3; sc: [k] = sin, cos), lanes 3 .. N + 3 take phi*_k.  A sincos of one argument is the same
+// value on any lane, so each of these is the value the separate calls gave.
+//
+// park (PARK; 4 doubles that outlive the solve): stage 0's atan2(omega lf + vy, vx_eff) and rear Pacejka sine at
+// x_0 (rollout lanes 0 / 1) and sin / cos(phi_0) (the phi pass), for plant_update_parked (mpc_frame.h).
 constexpr int TJ = 24;
 // Layout: one record of LREC doubles per stage, rec + LREC k = [A_k 36 | B_k 12 | g_k 6] on exit.  While
 // the stage is being formed the same record holds its scratch: the tire / sincos evaluations at [0, TJ) and
-// the rollout's (x_k, f_k) at [TJ, TJ + 12).  Only the lane that assembles stage k reads them, and it writes
-// the outputs after its reads, so no stage's scratch is overwritten before it is consumed.
+// the rollout's (x_k, f_k) at [TJ, TJ + 12).  Only the three lanes that assemble stage k read them, and a barrier
+// separates their reads from their writes of A_k, B_k, so no stage's scratch is overwritten before it is consumed.
+// The six sin / cos of u1, u1 +- eps wait at [36, 42) of stage 0's record (its B part) and are read before that
+// barrier as well.
 constexpr int LREC = 54;
 static_assert(TJ + 12 <= 36, "a stage's scratch must lie inside its record's A_k part");
-template <int NT>
+template <int NT, bool WIN = false, bool PARK = false>
 __device__ __forceinline__ void block_linearize(const int t, const VP& p, int N, double Ts, const double* xs,
-                                                const double* us, double* rec, long long* dbg = nullptr) {
+                                                const double* us, double* rec, long long* dbg = nullptr,
+                                                const double* phis = nullptr, double* sc = nullptr,
+                                                double* park = nullptr) {
     double* const tj = rec;                // [k]: rec + LREC k + [0, TJ)
     double* const xf = rec + TJ;           // [k]: rec + LREC k + TJ + [0, 12)
+    double* const usc = rec + 36;          // sin, cos of u1, u1 + eps, u1 - eps
     auto mark = [&](int i) { if (dbg && t == 0) dbg[i] = __builtin_amdgcn_s_memtime(); };
     const double eps = 1e-5;
+    // (lane roles below from a fresh copy of the thread index: derived from the caller's, they and the selects on them
+    // are invariants of the caller's item loop, kept live across the whole solve)
+    int tl;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(tl) : "v"(t));
+    // the sincos known up front, one argument per lane: l = 0 / 1 / 2: u1, u1 + eps, u1 - eps; l = 3 + k: phi*_k
+    double s_u1 = 0.0, c_u1 = 0.0;         // lane 0's: sin / cos(u1)
+    {
+        const double u1 = us[1];
+        const int nl = 3 + (WIN ? N + 1 : 0);
+        for (int l = tl; l < nl; l += NT) {
+            double arg;
+            if (l < 3) arg = (l == 0) ? u1 : ((l == 1) ? u1 + eps : u1 - eps);
+            else arg = phis[3 * (l - 3)];
+            double s, c;
+            pm_sincos(arg, &s, &c);
+            if (l < 3) {
+                usc[2 * l] = s;
+                usc[2 * l + 1] = c;
+                if (l == 0) { s_u1 = s; c_u1 = c; }
+            } else {
+                sc[2 * (l - 3)] = s;
+                sc[2 * (l - 3) + 1] = c;
+            }
+        }
+    }
     if (t < 64) {
         double x[6];
         for (int i = 2; i < 6; ++i) x[i] = xs[i];
         const double u0 = us[0], u1 = us[1];
-        double sd, cd;
-        pm_sincos(u1, &sd, &cd);
+        const double sd = readlane_d(s_u1, 0), cd = readlane_d(c_u1, 0);   // (thread 0 is this wave's lane 0)
         // this lane's role (see above): which tire, which input it perturbs
         const bool roll = t < 2;
         const bool fr = (t == 0) || (t == 3) || (t >= 5 && t <= 16 && ((t - 5) & 1) == 0) || t == 17 || t == 18;
@@ -314,6 +353,10 @@ __device__ __forceinline__ void block_linearize(const int t, const VP& p, int N,
                 if (!tire_sin_in_range(z)) sz = pm_sin(z);
             }
             if (t >= 3 && t <= 18) tj[LREC * k + t] = sz;
+            if (PARK && k == 0) {   // (uniform) what the plant's f(x_0, u_cmd) shares with this stage
+                if (t == 0) park[0] = at;
+                if (t == 1) park[1] = sz;
+            }
             const double Fy_f = p.Df * readlane_d(sz, 0), Fy_r = p.Dr * readlane_d(sz, 1);
             const double Frx = (p.Cm1 - p.Cm2 * vx) * u0 - p.Cr0 - p.Cr2 * (vx * vx);
             double f[6];
@@ -344,6 +387,10 @@ __device__ __forceinline__ void block_linearize(const int t, const VP& p, int N,
             const double vx = xf[LREC * k + 3], vy = xf[LREC * k + 4];
             xf[LREC * k + 6] = vx * cp - vy * sp;   // the rollout's f_0, f_1 at the raw phi_k
             xf[LREC * k + 7] = vx * sp + vy * cp;
+            if (PARK && k == 0) {   // sin / cos(phi_0 + -0.0) = sin / cos(phi_0)
+                park[2] = sp;
+                park[3] = cp;
+            }
         } else {
             T[18 + v] = sp;     // 19: phi + eps, 20: phi - eps
             T[v - 1] = cp;      // 0 / 1
@@ -364,72 +411,98 @@ __device__ __forceinline__ void block_linearize(const int t, const VP& p, int N,
     mark(20);
     mark(21);
     const double d = us[0], de = us[1];
-    // assembly: one stage per lane -- f at every perturbed point from the stored sines (f_parts, the
-    // reference's difference quotients), A = I + Ts Jx, B = Ts Ju, g = x + Ts f - A x - B u
-    double sd, cd, sdp, cdp, sdm, cdm;
-    pm_sincos(de, &sd, &cd);
-    pm_sincos(de + eps, &sdp, &cdp);
-    pm_sincos(de - eps, &sdm, &cdm);
-    for (int k = t; k < N; k += NT) {
-        const double* T = tj + LREC * k;
-        double xb[6], fk[6];
-        for (int i = 0; i < 6; ++i) { xb[i] = xf[LREC * k + i]; fk[i] = xf[LREC * k + 6 + i]; }
-        const double vx0 = xb[3] + 0.0, vy0 = xb[4] + 0.0, om0 = xb[5] + 0.0;
-        const double sphi = T[21], cphi = T[2];
-        const double Ff0 = p.Df * T[3], Fr0 = p.Dr * T[4], Fx0 = long_force(p, vx0, d);
-        double Ak[36], Bk[12], fp[6], fm[6];
-        for (int grp = 0; grp < 3; ++grp) {   // state columns (state_column)
-            const double vxp = grp == 0 ? xb[3] + eps : vx0, vxm = grp == 0 ? xb[3] - eps : vx0;
-            const double vyp = grp == 1 ? xb[4] + eps : vy0, vym = grp == 1 ? xb[4] - eps : vy0;
-            const double omp = grp == 2 ? xb[5] + eps : om0, omm = grp == 2 ? xb[5] - eps : om0;
-            const int l = 5 + 4 * grp;
-            f_parts(p, vxp, vyp, omp, sphi, cphi, sd, cd, p.Df * T[l], p.Dr * T[l + 1], long_force(p, vxp, d), fp);
-            f_parts(p, vxm, vym, omm, sphi, cphi, sd, cd, p.Df * T[l + 2], p.Dr * T[l + 3], long_force(p, vxm, d), fm);
-            for (int r = 0; r < 6; ++r) Ak[6 * r + 3 + grp] = a_entry(r, 3 + grp, Ts, cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV));
-        }
-        double Jphi[6], Jd[6], Jde[6];
-        // phi: only sin / cos(phi) change
-        f_parts(p, vx0, vy0, om0, T[19], T[0], sd, cd, Ff0, Fr0, Fx0, fp);
-        f_parts(p, vx0, vy0, om0, T[20], T[1], sd, cd, Ff0, Fr0, Fx0, fm);
-        for (int r = 0; r < 6; ++r) Jphi[r] = cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV);
-        // d: only the longitudinal force changes
-        f_parts(p, vx0, vy0, om0, sphi, cphi, sd, cd, Ff0, Fr0, long_force(p, vx0, d + eps), fp);
-        f_parts(p, vx0, vy0, om0, sphi, cphi, sd, cd, Ff0, Fr0, long_force(p, vx0, d - eps), fm);
-        for (int r = 0; r < 6; ++r) Jd[r] = cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV);
-        // delta: front force and sin / cos(delta) change
-        f_parts(p, vx0, vy0, om0, sphi, cphi, sdp, cdp, p.Df * T[17], Fr0, Fx0, fp);
-        f_parts(p, vx0, vy0, om0, sphi, cphi, sdm, cdm, p.Df * T[18], Fr0, Fx0, fm);
-        for (int r = 0; r < 6; ++r) Jde[r] = cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV);
-        // a -0.0 among the components the input columns pass through: those two columns on the
-        // reference's exact vectors, as cheap_columns does
-        if ((__builtin_signbit(xb[2]) && xb[2] == 0.0) || (__builtin_signbit(xb[3]) && xb[3] == 0.0) ||
-            (__builtin_signbit(xb[4]) && xb[4] == 0.0) || (__builtin_signbit(xb[5]) && xb[5] == 0.0) ||
-            (__builtin_signbit(d) && d == 0.0) || (__builtin_signbit(de) && de == 0.0)) {
-            for (int cu = 0; cu < 2; ++cu) {
-                const double up[2] = {cu == 0 ? d + eps : d + 0.0, cu == 1 ? de + eps : de + 0.0};
-                const double um[2] = {cu == 0 ? d - eps : d + 0.0, cu == 1 ? de - eps : de + 0.0};
+    // assembly: three lanes per stage -- f at this lane's perturbed points from the stored sines (f_parts, the
+    // reference's difference quotients), A = I + Ts Jx, B = Ts Ju, g = x + Ts f - A x - B u.  Lane 3 ks + c of a round
+    // of NT / 3 whole stages (one round up to N = 21 at 64 threads, N = 42 at 128): the state column c of
+    // state_column (vx, vy, omega -> A's column 3 + c) and the cheap column c of cheap_columns (phi -> A's column 2,
+    // d / delta -> B's columns 0 / 1).  The role only picks operands -- which component carries +-eps, which stored
+    // sine, sin / cos or longitudinal force enters f_parts -- so every entry sees the operations the one-lane
+    // assembly applied to it, on the same operands.
+    const double sd = usc[0], cd = usc[1], sdp = usc[2], cdp = usc[3], sdm = usc[4], cdm = usc[5];
+    constexpr int SPR = NT / 3;             // stages per round
+    const int ks = tl / 3, c = tl - 3 * ks;   // stage in the round, role
+    for (int k0 = 0; k0 < N; k0 += SPR) {
+        const int k = k0 + ks;
+        const bool act = ks < SPR && k < N;
+        double* const o = rec + LREC * k;
+        double xb[6], fk0 = 0.0, fk1 = 0.0, colS[6], colC[6];
+        if (act) {
+            const double* T = tj + LREC * k;
+            for (int i = 0; i < 6; ++i) xb[i] = xf[LREC * k + i];
+            fk0 = xf[LREC * k + 6 + 2 * c];   // the rollout's f_k, rows 2 c and 2 c + 1 (for g)
+            fk1 = xf[LREC * k + 7 + 2 * c];
+            const double vx0 = xb[3] + 0.0, vy0 = xb[4] + 0.0, om0 = xb[5] + 0.0;
+            const double sphi = T[21], cphi = T[2];
+            const double Fr0 = p.Dr * T[4];
+            double fp[6], fm[6];
+            {   // state column c (state_column)
+                const double vxp = c == 0 ? xb[3] + eps : vx0, vxm = c == 0 ? xb[3] - eps : vx0;
+                const double vyp = c == 1 ? xb[4] + eps : vy0, vym = c == 1 ? xb[4] - eps : vy0;
+                const double omp = c == 2 ? xb[5] + eps : om0, omm = c == 2 ? xb[5] - eps : om0;
+                const int l = 5 + 4 * c;
+                f_parts(p, vxp, vyp, omp, sphi, cphi, sd, cd, p.Df * T[l], p.Dr * T[l + 1], long_force(p, vxp, d), fp);
+                f_parts(p, vxm, vym, omm, sphi, cphi, sd, cd, p.Df * T[l + 2], p.Dr * T[l + 3], long_force(p, vxm, d), fm);
+                for (int r = 0; r < 6; ++r) colS[r] = a_entry(r, 3 + c, Ts, cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV));
+            }
+            // cheap column c: phi -- only sin / cos(phi) change (T[19], T[0] / T[20], T[1]); d -- only the longitudinal
+            // force (d +- eps); delta -- the front force (T[17] / T[18]) and sin / cos(delta +- eps).  What a column
+            // leaves alone is the base value: T[21], T[2]; Df T[3]; long_force(vx0, d); sd, cd.
+            const double sphp = T[c == 0 ? 19 : 21], cphp = T[c == 0 ? 0 : 2];
+            const double sphm = T[c == 0 ? 20 : 21], cphm = T[c == 0 ? 1 : 2];
+            const double Ffp = p.Df * T[c == 2 ? 17 : 3], Ffm = p.Df * T[c == 2 ? 18 : 3];
+            const double Fxp = long_force(p, vx0, c == 1 ? d + eps : d), Fxm = long_force(p, vx0, c == 1 ? d - eps : d);
+            f_parts(p, vx0, vy0, om0, sphp, cphp, c == 2 ? sdp : sd, c == 2 ? cdp : cd, Ffp, Fr0, Fxp, fp);
+            f_parts(p, vx0, vy0, om0, sphm, cphm, c == 2 ? sdm : sd, c == 2 ? cdm : cd, Ffm, Fr0, Fxm, fm);
+            double J[6];
+            for (int r = 0; r < 6; ++r) J[r] = cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV);
+            // a -0.0 among the components the input columns pass through: those two columns (the lanes c = 1, 2) on
+            // the reference's exact vectors, as cheap_columns does
+            if (c >= 1 &&
+                ((__builtin_signbit(xb[2]) && xb[2] == 0.0) || (__builtin_signbit(xb[3]) && xb[3] == 0.0) ||
+                 (__builtin_signbit(xb[4]) && xb[4] == 0.0) || (__builtin_signbit(xb[5]) && xb[5] == 0.0) ||
+                 (__builtin_signbit(d) && d == 0.0) || (__builtin_signbit(de) && de == 0.0))) {
+                const int cu = c - 1;
+                // (de through an opaque move: f_cont's sin / cos(u_1) depend on the role and the input alone, and
+                // would otherwise be hoisted out of this rare branch and evaluated by every item)
+                double deo = de;
+                asm volatile("" : "+v"(deo));
+                const double up[2] = {cu == 0 ? d + eps : d + 0.0, cu == 1 ? deo + eps : deo + 0.0};
+                const double um[2] = {cu == 0 ? d - eps : d + 0.0, cu == 1 ? deo - eps : deo + 0.0};
                 double xc[6];
                 for (int i = 0; i < 6; ++i) xc[i] = xb[i];
                 f_cont(p, xc, up, fp);
                 f_cont(p, xc, um, fm);
-                for (int r = 0; r < 6; ++r) (cu == 0 ? Jd : Jde)[r] = cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV);
+                for (int r = 0; r < 6; ++r) J[r] = cdiv(fp[r] - fm[r], 2.0 * eps, DQ_INV);
+            }
+            for (int r = 0; r < 6; ++r) colC[r] = (c == 0) ? a_entry(r, 2, Ts, J[r]) : Ts * J[r];
+        }
+        __syncthreads();   // every read of the round's scratch (and of usc) precedes the writes over it
+        if (act) {
+            for (int r = 0; r < 6; ++r) {
+                o[6 * r + 3 + c] = colS[r];
+                o[(c == 0) ? 6 * r + 2 : 36 + 2 * r + (c - 1)] = colC[r];
+            }
+            for (int j = 0; j < 2; ++j) {   // the X, Y columns: rows 2 c, 2 c + 1
+                const int r = 2 * c + j;
+                o[6 * r + 0] = a_entry(r, 0, Ts, 0.0);
+                o[6 * r + 1] = a_entry(r, 1, Ts, 0.0);
             }
         }
-        for (int r = 0; r < 6; ++r) {
-            Ak[6 * r + 0] = a_entry(r, 0, Ts, 0.0);
-            Ak[6 * r + 1] = a_entry(r, 1, Ts, 0.0);
-            Ak[6 * r + 2] = a_entry(r, 2, Ts, Jphi[r]);
-            Bk[2 * r + 0] = Ts * Jd[r];
-            Bk[2 * r + 1] = Ts * Jde[r];
+        __syncthreads();
+        if (act) {   // g_stage's rows 2 c and 2 c + 1 from the stage's finished A_k, B_k
+            for (int j = 0; j < 2; ++j) {
+                const int r = 2 * c + j;
+                double ax = 0.0, bu = 0.0;
+                for (int cc = 0; cc < 6; ++cc) ax += o[6 * r + cc] * xb[cc];
+                bu += o[36 + 2 * r] * d;
+                bu += o[36 + 2 * r + 1] * de;
+                const double xr = (j == 0) ? (c == 0 ? xb[0] : (c == 1 ? xb[2] : xb[4]))
+                                           : (c == 0 ? xb[1] : (c == 1 ? xb[3] : xb[5]));
+                o[48 + r] = xr + Ts * (j == 0 ? fk0 : fk1) - ax - bu;
+            }
         }
-        double gk[6];
-        g_stage(Ak, Bk, xb, fk, d, de, Ts, gk);
-        double* const o = rec + LREC * k;   // (after every read of this stage's scratch)
-        for (int i = 0; i < 36; ++i) o[i] = Ak[i];
-        for (int i = 0; i < 12; ++i) o[36 + i] = Bk[i];
-        for (int r = 0; r < 6; ++r) o[48 + r] = gk[r];
+        __syncthreads();
     }
-    __syncthreads();
 }
 
 }  // namespace tgmpc

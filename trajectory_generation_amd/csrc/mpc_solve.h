@@ -196,12 +196,18 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     double* const s_sc = CMP ? s_u + NFS + 4 * (NM + 1) : (L2W ? s_big + NLIN + 4 * (NM + 1) : s_sc0);
     __shared__ double s_red[WAVES > 1 ? 16 * WAVES : 2];
     __shared__ int s_flag[4];
-    // The static LDS image of a fused one-wave instance (CMP): s_big, s_u, s_x0, s_up, s_xh, s_item (padded to 8 bytes)
-    // and s_flag -- the 2-double placeholders above and s_red have no reader there and take no space.  It decides the
-    // occupancy the kernel is tuned for, of a CU's 160 KB: at capacity 40, 8 workgroups (2 waves per SIMD) need
-    // <= 20,480 B and 12 (the 3-wave instance) <= 12,800 B; the images are 19,784 B and 12,776 B, the compiler's
-    // group_segment_fixed_size.
-    constexpr int LDS_CMP = sizeof(s_big) + sizeof(s_u) + sizeof(s_x0) + sizeof(s_up) + sizeof(s_xh) + 8 + sizeof(s_flag);
+    // PARK: stage 0's atan2, rear tire sine and sin / cos(phi_0) of the in-workgroup linearization, kept for the plant
+    // update at the item's end (plant_update_parked) -- 32 bytes that outlive the solve.  The 3-wave instance's image
+    // has 24 bytes to spare: it keeps the plant that evaluates f(x_0, u_cmd) whole.
+    constexpr bool PARK = CLOSED && INLIN && !(CMP && WPS >= 3);
+    __shared__ double s_park[PARK ? 4 : 1];
+    // The static LDS image of a fused one-wave instance (CMP): s_big, s_u, s_x0, s_up, s_xh, s_item (padded to 8 bytes),
+    // s_flag and (PARK) s_park -- the 2-double placeholders above and s_red have no reader there and take no space.
+    // It decides the occupancy the kernel is tuned for, of a CU's 160 KB: at capacity 40, 8 workgroups (2 waves per
+    // SIMD) need <= 20,480 B and 12 (the 3-wave instance) <= 12,800 B; the images are 19,816 B and 12,776 B, the
+    // compiler's group_segment_fixed_size.
+    constexpr int LDS_CMP = sizeof(s_big) + sizeof(s_u) + sizeof(s_x0) + sizeof(s_up) + sizeof(s_xh) + 8 + sizeof(s_flag) +
+                            (PARK ? sizeof(s_park) : 0);
     static_assert(!(CMP && NN == 40 && WPS == 2) || LDS_CMP <= 20480, "LDS image: 8 workgroups per CU");
     static_assert(!(CMP && NN == 40 && WPS >= 3) || LDS_CMP <= 12800, "LDS image: 12 workgroups per CU");
 
@@ -452,7 +458,9 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // A_k, B_k, g_k staged in LDS (coalesced copy); rows are then read as uniform broadcasts
     if constexpr (INLIN) {
         // A_k, B_k, g_k as stage records (LREC doubles each) in s_big
-        block_linearize<NT>(t, p, N, Ts, s_x0, s_up, s_big, dbg ? dbg + (size_t)b * 32 : nullptr);
+        // (with the sin / cos of the window's phi*_k on its up-front sincos lanes, and the plant's stage-0 values parked)
+        block_linearize<NT, true, PARK>(t, p, N, Ts, s_x0, s_up, s_big, dbg ? dbg + (size_t)b * 32 : nullptr,
+                                        s_pref + 2, s_sc, s_park);
         if constexpr (!FUSED) {
             // the step entry point reports X_opt by the linear model (read back from A/B/g at the end)
             double* const wA = const_cast<double*>(gA);
@@ -495,12 +503,14 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     const double* const cA = s_big;
     const double* const cB = s_big + (INLIN ? 36 : 36 * N);
     const double* const cg = s_big + (INLIN ? 48 : 48 * N);
-    // sin / cos of phi*_k for every stage (lane-parallel)
-    for (int k = t; k <= N; k += NT) {
-        double sk, ck;
-        pm_sincos(s_pref[3 * k + 2], &sk, &ck);
-        s_sc[2 * k] = sk;
-        s_sc[2 * k + 1] = ck;
+    // sin / cos of phi*_k for every stage (lane-parallel; INLIN: block_linearize formed them)
+    if constexpr (!INLIN) {
+        for (int k = t; k <= N; k += NT) {
+            double sk, ck;
+            pm_sincos(s_pref[3 * k + 2], &sk, &ck);
+            s_sc[2 * k] = sk;
+            s_sc[2 * k + 1] = ck;
+        }
     }
     __syncthreads();
     stamp(17, __builtin_amdgcn_s_memtime());
@@ -1807,7 +1817,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     if (CLOSED) {
         // plant x <- x + Ts f(x, u_cmd) (main.py:97), u_prev <- u_cmd (:101)
         if (t == 0) {
-            plant_step<FUSED>(a, b, step, tstep, s_x0, uc0, uc1, status, iter);
+            plant_step<FUSED, PARK>(a, b, step, tstep, s_x0, uc0, uc1, status, iter, s_park);
             if (FUSED) {
                 if (step == a.nsteps - 1) stamp(23, __builtin_amdgcn_s_memrealtime());   // launch span
                 if (dbg_items) dbg_items[4 * (size_t)item_of_wave + 2] = __builtin_amdgcn_s_memrealtime();
