@@ -16,7 +16,8 @@
 //     non-finite or (0, 0) arguments take the device library's atan2 for that lane.
 // Accuracy against 80-bit references (tools/microbench/fastmath_check.hip, 4 M points per range on the GPU): see
 // DESIGN.md (the device library's own routines: 0.8 ulp sin / cos, 1.5 atan, 1.6 atan2).  The reference path's own functions are numpy's (glibc):
-// the physics fixtures are checked at 1e-12 relative and the difference quotients at 1e-8 (tests/).
+// the physics fixtures are checked at 1e-12 relative; f and the difference quotients are held to an mpmath reference
+// at 11.4 S_r 2^-52 and 12.3 Ts S_rj 2^-52 / (2 eps), S the abs-sum of f_r's terms (tests/_lin_ref.py).
 // Every caller in the MPC path (fused and per-step kernels, the physics entry points, the window kernels) uses
 // these, so the fused closed loop and the per-step launches stay bit-identical.
 #pragma once
