@@ -70,7 +70,12 @@ typedef struct {
 } traj_vehicle_params;
 
 /* mpc_step keyword arguments (mpc_6stati.py:120-143) + QP solver settings.  Solver defaults are
- * CVXPY's OSQP settings (eps_abs = eps_rel = 1e-5, max_iter = 10000, polish on). */
+ * CVXPY's OSQP settings (eps_abs = eps_rel = 1e-5, max_iter = 10000, polish on).
+ * Accepted ranges (OSQP's own; anything else, NaN included, is TRAJ_E_ARG from every entry point before any launch
+ * and 0 from the workspace queries): Ts > 0; rho, sigma, delta > 0; 0 < alpha < 2; eps_abs, eps_rel >= 0 and not
+ * both zero; eps_prim_inf > 0; max_iter >= 1; check_interval >= 1; scaling_iters >= 0; adaptive_rho_tol >= 1;
+ * polish_refine_iter, polish_max_pass, polish_max_rounds >= 0; cert_tol >= 0; polish_mode 0 or 1.  polish,
+ * adaptive_rho and warm_start are flags (zero / non-zero). */
 typedef struct {
     int N;                            /* horizon: 1 <= N <= TRAJ_MAX_N_GENERAL for every entry point (the solver
                                        * by N: "Horizon tiers" below) */
@@ -88,7 +93,8 @@ typedef struct {
     int max_iter, check_interval, scaling_iters, polish, polish_refine_iter, adaptive_rho;
     double adaptive_rho_tol;
     int polish_mode;                  /* 0: OSQP polish; 1: exact polish (KKT-certified optimum) */
-    int polish_max_pass;
+    int polish_max_pass;              /* exact mode: active-set passes 1 .. polish_max_pass per round (0: no pass
+                                       * certifies; the continuation rounds run, the point stays unpolished) */
     double cert_tol;
     int polish_max_rounds;
     int warm_start;                   /* closed loop: start ADMM from the previous step's adapted rho

@@ -28,6 +28,11 @@ static traj_mpc_config config(int N, bool bounds) {
     c.max_iter = 200;
     c.check_interval = 25;
     c.scaling_iters = 10;
+    // the solver settings check_cfg holds to OSQP's ranges: traj_default_config's values
+    c.eps_abs = 1e-5; c.eps_rel = 1e-5; c.eps_prim_inf = 1e-4;
+    c.rho = 0.1; c.sigma = 1e-6; c.alpha = 1.6; c.delta = 1e-6;
+    c.polish = 1; c.polish_refine_iter = 3; c.adaptive_rho = 1; c.adaptive_rho_tol = 5.0;
+    c.polish_max_pass = 8; c.cert_tol = 1e-9; c.polish_max_rounds = 2;
     if (bounds) {   // x_lo given, one finite entry
         c.has_x_lo = 1;
         for (int i = 0; i < 6; ++i) c.x_lo[i] = -1e30;

@@ -236,6 +236,49 @@ def test_argument_errors_are_reported_before_any_launch(L):
                   nul) == _lib.TRAJ_OK
         assert fn(C.byref(p), C.byref(cLx), C.byref(ps), 0, nul, nul, nul, *extra, 0, nul, nul, nul, nul, nul, 0,
                   nul) == _lib.TRAJ_E_ARG
+    # solver settings outside OSQP's own ranges (include/trajmpc.h, next to the struct), one at a time on an otherwise
+    # default configuration: every entry refuses them (B = 0: nothing could launch if one were accepted) and the
+    # three workspace queries return 0; NaN fails every comparison
+    nan, inf = float("nan"), float("inf")
+    bad = [("rho", 0.0), ("rho", -0.1), ("rho", nan), ("sigma", 0.0), ("sigma", -1e-6), ("sigma", nan),
+           ("delta", 0.0), ("delta", -1e-6), ("delta", nan), ("alpha", 0.0), ("alpha", 2.0), ("alpha", -1.6),
+           ("alpha", nan), ("alpha", inf), ("eps_abs", -1e-5), ("eps_abs", nan), ("eps_rel", -1e-5), ("eps_rel", nan),
+           ("eps_prim_inf", 0.0), ("eps_prim_inf", -1e-4), ("eps_prim_inf", nan), ("adaptive_rho_tol", 0.5),
+           ("adaptive_rho_tol", nan), ("polish_refine_iter", -1), ("polish_max_pass", -1), ("polish_max_rounds", -1),
+           ("cert_tol", -1e-9), ("cert_tol", nan), ("max_iter", 0), ("check_interval", 0), ("scaling_iters", -1),
+           ("polish_mode", 2), ("Ts", nan)]
+
+    def entries(cf):
+        return [L.traj_mpc_step_batch(C.byref(p), C.byref(cf), 0, *([nul] * 11), nul, 0, nul),
+                L.traj_mpc_qp_batch(C.byref(p), C.byref(cf), 0, *([nul] * 14), nul, 0, nul),
+                L.traj_closed_loop_step(C.byref(p), C.byref(cf), C.byref(ps), 0, nul, nul, nul, 0, 0, nul, nul, nul,
+                                        nul, nul, 0, nul),
+                L.traj_closed_loop_run(C.byref(p), C.byref(cf), C.byref(ps), 0, nul, nul, nul, 0, 1, 0, nul, nul, nul,
+                                       nul, nul, 0, nul)]
+
+    def queries(cf):
+        return [q(C.byref(cf), 4) for q in (L.traj_mpc_step_workspace_bytes, L.traj_mpc_qp_workspace_bytes,
+                                            L.traj_closed_loop_workspace_bytes)]
+
+    for N in (20, 65):         # 65: every query has a size to withhold (the QP entry needs none at N = 20)
+        for field, v in bad + [("eps_abs+eps_rel", 0.0)]:
+            cb = _lib.default_config(N, 0.05)
+            for f in field.split("+"):
+                setattr(cb, f, v)
+            assert entries(cb) == [_lib.TRAJ_E_ARG] * 4, (N, field, v)
+            assert queries(cb) == [0, 0, 0], (N, field, v)
+        # the ends of the ranges that are allowed: one eps at zero, adaptive_rho_tol = 1, the counts at zero
+        for kw in (dict(eps_abs=0.0), dict(eps_rel=0.0), dict(adaptive_rho_tol=1.0), dict(cert_tol=0.0),
+                   dict(polish_refine_iter=0, polish_max_pass=0, polish_max_rounds=0), dict(alpha=1.0)):
+            cb = _lib.default_config(N, 0.05)
+            for f, v in kw.items():
+                setattr(cb, f, v)
+            assert entries(cb) == [_lib.TRAJ_OK] * 4, (N, kw)
+    for N in (1, 20, 1024):
+        cd = _lib.default_config(N, 0.05)
+        assert entries(cd) == [_lib.TRAJ_OK] * 4, N
+        q = queries(cd)
+        assert q[0] > 0 and q[2] > 0 and (q[1] > 0) == (N > _lib.MAX_N), (N, q)
 
 
 ROUTE_GOLDEN = os.path.join(ROOT, "tests", "golden", "route_parent.npz")

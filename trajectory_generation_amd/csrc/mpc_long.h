@@ -535,7 +535,7 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
                 v[1] = own ? fmax(fabs(Dinv * qi), fabs(Dinv * Pxv)) * csinv : 0.0;  // gradient scale
                 block_max(v);
                 const double gsc = fmax(1.0, v[1]);
-                int okc = v[0] <= tol * gsc;
+                int okc = pass_counts(c) && v[0] <= tol * gsc;
                 if (own) {
                     const double axu = axb * Ebinv, arv = axr * Erinv;
                     if (slb > -INFTY && axu < lb_ - tol * (1.0 + fabs(lb_))) okc = 0;

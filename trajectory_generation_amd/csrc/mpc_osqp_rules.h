@@ -38,6 +38,10 @@ __device__ __forceinline__ int active_sign(double z, double l, double u, double 
     return (z - l < -y) ? -1 : ((u - z < y) ? 1 : 0);
 }
 
+// exact mode: can this pass's certificate count?  The passes are 1 .. polish_max_pass, so with polish_max_pass = 0 none
+// does -- the point stays uncertified and the continuation rounds run (the oracle's and mpc_general.h's pass loop)
+__device__ __forceinline__ bool pass_counts(const traj_mpc_config& c) { return c.polish_max_pass >= 1; }
+
 // after an uncertified or failed polish: continue ADMM to a 100x tighter tolerance, then polish again?
 __device__ __forceinline__ bool polish_continues(const traj_mpc_config& c, int rounds, int iter) {
     return rounds < c.polish_max_rounds && iter < c.max_iter;

@@ -54,6 +54,12 @@ inline int check_cfg(const traj_mpc_config* c) {
     if (c->N < 1 || c->N > TRAJ_MAX_N_GENERAL) return TRAJ_E_ARG;
     if (!(c->Ts > 0.0) || c->max_iter < 1 || c->check_interval < 1 || c->scaling_iters < 0) return TRAJ_E_ARG;
     if (c->polish_mode != 0 && c->polish_mode != 1) return TRAJ_E_ARG;
+    // the solver settings OSQP itself validates (osqp_api: validate_settings), each written so that NaN fails
+    if (!(c->rho > 0.0) || !(c->sigma > 0.0) || !(c->delta > 0.0)) return TRAJ_E_ARG;
+    if (!(c->alpha > 0.0 && c->alpha < 2.0)) return TRAJ_E_ARG;
+    if (!(c->eps_abs >= 0.0) || !(c->eps_rel >= 0.0) || (c->eps_abs == 0.0 && c->eps_rel == 0.0)) return TRAJ_E_ARG;
+    if (!(c->eps_prim_inf > 0.0) || !(c->adaptive_rho_tol >= 1.0) || !(c->cert_tol >= 0.0)) return TRAJ_E_ARG;
+    if (c->polish_refine_iter < 0 || c->polish_max_pass < 0 || c->polish_max_rounds < 0) return TRAJ_E_ARG;
     return TRAJ_OK;
 }
 

@@ -1735,7 +1735,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
                 v[1] = own ? fmax(fabs(Dinv * qi), fabs(Dinv * Pxv)) * csinv : 0.0;  // gradient scale
                 block_max(v);
                 double gsc = fmax(1.0, v[1]);
-                int okc = v[0] <= tol * gsc;
+                int okc = pass_counts(c) && v[0] <= tol * gsc;
                 if (own) {
                     double axu = axb * Ebinv, arv = axr * Erinv;
                     if (slb > -INFTY && axu < lb - tol * (1.0 + fabs(lb))) okc = 0;

@@ -988,7 +988,8 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
                 v[1] = own ? fmax(fabs(Dinv * qi), fabs(Dinv * Pxv)) * csinv : 0.0;  // gradient scale
                 block_max(v);
                 const double gsc = fmax(1.0, v[1]);
-                int okc = v[0] <= tol * gsc;
+                // (the passes are 1 .. polish_max_pass: with 0 none certifies, as pass_counts of mpc_osqp_rules.h)
+                int okc = c.polish_max_pass >= 1 && v[0] <= tol * gsc;
                 if (own) {
                     const double axu = axb * Ebinv, arv = axr * Erinv;
                     if (slb > -INFTY && axu < lb_ - tol * (1.0 + fabs(lb_))) okc = 0;
