@@ -9,9 +9,13 @@ The checks hold a solver's outputs to the QP itself (tests/_qp_ref.py), not to a
   * the inequality rows: 1e-9 where polished, else eps_abs + eps_rel max||[U; dU]||_inf -- OSQP's unscaled primal
     criterion: the returned point is x, whose distance to the box is at most ||Ax - z||_inf;
   * status > 1: X_opt, U_opt, objective NaN and u_cmd = u_prev (mpc_6stati.py:257-262);
-  * polished points: |cost(U) - J*| <= 1e-7 |J*| with J* from the oracle's sparse-form Riccati IPM (a different
-    algorithm, pinned to the reference goldens by test_sparse_structured_ipm_vs_golden); 1e-7 is the project's
-    objective bar (tests/test_oracle_golden.py).
+  * polished points without state rows: |cost(U) - J*| <= 1e-7 |J*| with J* from the oracle's sparse-form Riccati
+    IPM (a different algorithm, pinned to the reference goldens by test_sparse_structured_ipm_vs_golden); 1e-7 is
+    the project's objective bar (tests/test_oracle_golden.py);
+  * polished points, state rows or not: the weak-duality certificate (certify_point) -- a dual bound d <= J* from
+    multipliers fitted to the point's own active rows, J - d <= 1e-7 |J|, in numpy alone.  This is what holds the
+    general solver's state-bound solves and the bounded closed loop's steps to the optimum, which the IPM (it has
+    no state rows) cannot; on the other tiers it stands beside the IPM, whose code is the project's.
 
 C_X and C_J are 4x the worst error-over-bar ratio that tests/test_qp_ref.py measures on the CPU for the oracle over
 this case table (that test asserts 4 x worst <= C; the goldens' objective is held to the same quarter bar): the margin
@@ -19,11 +23,12 @@ is for a GPU epilogue summing in another order and contracting to fma.  Measured
 objective 0.0847 (oracle; goldens 0.036).  The golden X_opt is a solver's output, exact to its recorded KKT residual
 (1.4e-12) and not to rounding, so it pins the rollout at 1e-11 (1 + S) and takes no part in C_X.  Neither constant is
 taken from a kernel's numbers (the kernels measure X 0.108, objective 0.152: DESIGN.md section 2, "Output checks").
+The certificate's C_D and C_JC are made by the same rule (below, beside certify_point).
 
 The solver-settings rows (tests/_settings_cases.py) run the same checks with the row's own eps_abs / eps_rel in the
 unpolished bar (10 x for status 1, OSQP's "inaccurate" criterion), their own pair of constants C_X_SET / C_J_SET made
-by the same rule, and the polished 1e-9 bar and the gap only where that table lists them; parity / pooled hold a call
-to the oracle under the same settings with the bars of tests/test_gpu_parity.py.
+by the same rule, and the polished 1e-9 bar, the gap and the certificate only where that table lists them; parity /
+pooled hold a call to the oracle under the same settings with the bars of tests/test_gpu_parity.py.
 """
 from __future__ import annotations
 
@@ -50,17 +55,37 @@ NONDEFAULT = dict(q_c=11.0, q_phi=0.2, q_vx=1.7, R=[[.05, .03], [.03, 1.1]], Rd=
 NONDEFAULT_PARAMS = {"m": 0.05, "Iz": 3.1e-5, "lf": 0.03}
 # a non-symmetric R with NONDEFAULT's symmetric part (the header: the symmetric part is used)
 NONSYM_R = [[.05, .05], [.01, 1.1]]
+_INF = np.inf
+
+
+def _sb(lo, hi):
+    return dict(x_lo=[-_INF if v is None else v for v in lo], x_hi=[_INF if v is None else v for v in hi])
+
+
+# further kinds of state bound: "wide" is tests/test_gpu_parity.py's SB (vx, vy, omega); one state each for omega and
+# vy; "phi_hi" bounds one side only, of a state the cost rows also touch (the path's heading passes 0.3 where the
+# window runs out to |x| > 1.5: tests/_cases.py)
 SETTINGS = {"default": ({}, None),
             "vx": (dict(x_lo=SB_VX[0], x_hi=SB_VX[1]), None),
+            "wide": (_sb([None, None, None, 0.35, -0.3, -3.0], [None, None, None, 1.6, 0.3, 3.0]), None),
+            "omega": (_sb([None] * 5 + [-1.0], [None] * 5 + [1.0]), None),
+            "vy": (_sb([None] * 4 + [-0.05, None], [None] * 4 + [0.05, None]), None),
+            "phi_hi": (dict(x_hi=[_INF, _INF, 0.3, _INF, _INF, _INF]), None),
             "nondefault": (NONDEFAULT, NONDEFAULT_PARAMS),
             "nonsym": (dict(NONDEFAULT, R=NONSYM_R), NONDEFAULT_PARAMS)}
 
 
+def state_bounded(kw):
+    """The mpc_step arguments carry state rows (the general solver runs)."""
+    return kw.get("x_lo") is not None or kw.get("x_hi") is not None
+
+
 class Case(NamedTuple):
     """One row of the table.  route: how the kernel is selected ("default"; "cap80": traj_debug_split_min_n(41) on
-    the step entry; "long_lds": traj_debug_split_max_n(0)).  gap: the polish modes in which the optimality gap is
-    asserted with its coverage condition ((1,): certified points only -- at Ts = 0.05 from N = 48 up and at
-    N >= 200 OSQP mode accepts its polish too rarely, and what it accepts need not be the optimum: tests/test_qp_ref.py)."""
+    the step entry; "long_lds": traj_debug_split_max_n(0)).  gap: the polish modes in which the optimality gap and
+    the certificate are asserted with their coverage condition (state-bound rows: the certificate in both; (1,):
+    certified points only -- at Ts = 0.05 from N = 48 up and at N >= 200 OSQP mode accepts its polish too rarely, and
+    what it accepts need not be the optimum: tests/test_qp_ref.py)."""
     kernel: str
     N: int
     Ts: float
@@ -77,8 +102,10 @@ class Case(NamedTuple):
 
 
 # seeds: from 17 up, taken where the ORACLE ALONE -- on the CPU, tests/test_qp_ref.py -- polishes at least half (and two)
-# of the status <= 1 instances in every mode listed in `gap`, each of those within 1e-7 of the IPM's optimum, and (the
-# general solver's rows) stops well before the iteration cap; what the rejected seeds show is in that file's docstring
+# of the status <= 1 instances in every mode listed in `gap`, each of those within 1e-7 of the IPM's optimum and
+# certified, (state-bound rows) has two instances whose state rows carry multipliers, two on which the unbounded
+# optimum breaks a state row, and no instance the margin LP calls borderline, and (the general solver's rows) stops
+# well before the iteration cap; what the rejected seeds show is in that file's docstring
 QP_CASES = [
     Case("onewave", 1, 0.02, 16, 17), Case("onewave", 8, 0.02, 16, 17), Case("onewave", 20, 0.02, 16, 17),
     Case("onewave", 20, 0.05, 16, 17),
@@ -93,6 +120,12 @@ QP_CASES = [
     Case("general", 300, 0.02, 3, 35, gap=(1,)),
     Case("general_sb", 20, 0.02, 16, 17, settings="vx"), Case("general_sb", 40, 0.02, 12, 17, settings="vx"),
     Case("general_sb", 65, 0.02, 8, 21, settings="vx"),
+    # the other kinds of state bound (SETTINGS); "wide" at Ts = 0.05: ADMM's certificate decides 5 of the 16 instances.
+    # ("omega" at N = 40, Ts = 0.02 is left out: the oracle runs to the iteration cap on an instance of seed 17)
+    Case("general_sb", 20, 0.02, 16, 17, settings="wide"), Case("general_sb", 20, 0.05, 16, 17, settings="wide"),
+    Case("general_sb", 20, 0.02, 16, 17, settings="omega"),
+    Case("general_sb", 20, 0.02, 16, 17, settings="vy"), Case("general_sb", 40, 0.02, 12, 17, settings="vy"),
+    Case("general_sb", 20, 0.02, 16, 17, settings="phi_hi"),
 ]
 # the step entry: 21 <= N <= 40 runs the row-split kernel (H = 40) by default and the capacity-80 kernel on request
 STEP_CASES = ([c._replace(kernel="split40") if c.kernel == "cap80" else c for c in QP_CASES]
@@ -292,7 +325,7 @@ def check_gap(O, o, case, lin, require=True):
     instances and on at least two.  Returns the worst relative gap."""
     x0, up, pr, vr = inputs_of(case)
     kw = SETTINGS[case.settings][0]
-    assert "x_lo" not in kw and "x_hi" not in kw, "the IPM has no state rows"
+    assert not state_bounded(kw), "the IPM has no state rows: check_certificate"
     ok = o["status"] <= 1
     pol = ok & (o["polished"] > 0)
     if require:
@@ -308,3 +341,123 @@ def check_gap(O, o, case, lin, require=True):
         worst = max(worst, gap)
         assert gap <= GAP_TOL, (case.id, b, "optimality gap", gap, J, r["objective"])
     return worst
+
+
+# ---- the weak-duality certificate: optimality with no solver on the other side
+
+# 4 x the oracle's worst ratio over tests/test_qp_ref.py's and tests/test_settings_ref.py's CPU surveys (both assert
+# 4 x worst <= C): (b) 0.0148 (N = 20, Ts = 0.05, the "combined" settings row), (c) 0.0462 (N = 8).  Never a kernel's.
+C_D = 0.06
+C_JC = 0.19
+
+
+def certify_point(qp, U, J, Ja, N, tag, c_d=C_D, c_jc=C_JC):
+    """One point U [2,N] against qp = Q.condensed(...) of its instance; J, Ja = Q.cost(Q.rollout(U), U).  Asserts
+      (a) Jc - d <= GAP_TOL |Jc|: Jc the condensed objective at U, d the dual bound of Q.certificate's multipliers --
+          d <= J* <= Jc, so the point is proved optimal to the bar;
+      (b) Jc - d >= -(|y|_1 viol + c_d (2N + 8) 2^-52 (Ja + Da)): weak duality read the other way -- at a point that
+          breaks its rows by at most viol, L(u, y) >= Jc - |y|_1 viol, and rounding does the rest (a d above that
+          means the bound itself was formed wrongly).  Da is the dual expression's own abs-sum scale
+          (Q.dual_bound): with Ja alone the oracle's own points reach 35 x the C = 1 bar at N = 65 -- d solves with
+          the condensed Hessian, and the cost's scale at the point does not follow what that rounds;
+      (c) |Jc - J| <= c_jc (2N + 8) 2^-52 (Ja + Jca): the condensed form is the QP that `cost` and `rollout` state.
+          Jca is the condensed expression's own abs-sum scale, 1/2 |u|' |P| |u| + |q|' |u| + |c0|: it is evaluated
+          about U = 0, where c0, q' u and u' P u cancel down to J (Jca / Ja reaches 350 at N = 49), so Ja alone is
+          not the size of what it rounds (against C_J (N + 8) 2^-52 Ja the oracle's own points measure 2.3).
+    Returns (relative gap, ratio of (b) with c_d = 1, ratio of (c) with c_jc = 1, state rows with a positive multiplier,
+    d)."""
+    P, q, c0, A, lo, hi, ns = qp
+    u = Q.stage_major(U)
+    ce = Q.certificate(P, q, c0, A, lo, hi, u, ns)
+    r = A @ u
+    viol = float(max(np.max(lo - r), np.max(r - hi), 0.0))
+    y1 = float(ce["y_plus"].sum() + ce["y_minus"].sum())
+    au = np.abs(u)
+    Jca = float(0.5 * au @ np.abs(P) @ au + np.abs(q) @ au + abs(c0))
+    fac = (2 * N + 8) * EPS
+    gap = ce["J"] - ce["d"]
+    rel = gap / abs(ce["J"])
+    rd = max(0.0, -gap - y1 * viol) / (fac * (Ja + ce["d_scale"]))
+    rjc = abs(ce["J"] - J) / (fac * (Ja + Jca))
+    assert rel <= GAP_TOL, (tag, "certificate gap", rel, ce["J"], ce["d"])
+    assert rd <= c_d, (tag, "dual bound above the objective", rd, c_d, gap, y1, viol)
+    assert rjc <= c_jc, (tag, "condensed objective vs cost(rollout(U), U)", rjc, c_jc, ce["J"], J)
+    return rel, rd, rjc, ce["n_state_active"], ce["d"]
+
+
+_QP = {}
+
+
+def qp_of(case, lin, b):
+    """Q.condensed of instance b of the case on the oracle's linearization (computed once: lin is lin_of's)."""
+    key = (case.N, case.Ts, case.B, case.seed, case.settings, case.variant, b)
+    if key not in _QP:
+        x0, up, pr, vr = inputs_of(case)
+        _QP[key] = Q.condensed(x0[b], lin[0][b], lin[1][b], lin[2][b], up[b], pr[b], vr[b], SETTINGS[case.settings][0])
+    return _QP[key]
+
+
+def certify_outputs(o, inputs, lin, kw, N, tag, c_d=C_D, c_jc=C_JC, qp=None):
+    """Every instance of one call's outputs `o` with status <= 1 and polished > 0 through certify_point, state rows
+    or not.  inputs = (x0, u_prev, path_ref, vref) of the call, lin its linearization, kw its mpc_step arguments;
+    qp(b): the condensed QP of instance b where the caller keeps it.  Returns (worst relative gap, Worst ratios of
+    (b) and (c), number of instances with a state row carrying a positive multiplier, {b: dual bound})."""
+    x0, up, pr, vr = inputs
+    pol = (o["status"] <= 1) & (o["polished"] > 0)
+    w, worst, n_state, bound = Worst(), -np.inf, 0, {}
+    for b in np.where(pol)[0]:
+        X, _ = Q.rollout(x0[b], lin[0][b], lin[1][b], lin[2][b], o["U_opt"][b])
+        J, Ja = Q.cost(X, o["U_opt"][b], up[b], pr[b], vr[b], kw)
+        cond = qp(b) if qp else Q.condensed(x0[b], lin[0][b], lin[1][b], lin[2][b], up[b], pr[b], vr[b], kw)
+        rel, rd, rjc, ns, bound[b] = certify_point(cond, o["U_opt"][b], J, Ja, N, f"{tag} b={b}", c_d, c_jc)
+        worst = max(worst, rel)
+        w.add("D", rd)
+        w.add("Jc", rjc)
+        n_state += ns > 0
+    return worst, w, n_state, bound
+
+
+def check_certificate(o, case, lin, require=True, c_d=C_D, c_jc=C_JC, min_state=2):
+    """certify_outputs on a case of the table.  require: the coverage condition -- check_gap's (polished on at least
+    half of the status <= 1 instances and on two) and, with state bounds, at least min_state = two instances with a
+    state row carrying a positive multiplier: the certificate then rests on the state rows' signs and on the active
+    set the solver chose (min_state = 0: the settings rows tests/_settings_cases.py NO_STATE_ROWS lists, where the
+    oracle's own polished points have none).  Returns certify_outputs' tuple."""
+    kw = SETTINGS[case.settings][0]
+    ok = o["status"] <= 1
+    pol = ok & (o["polished"] > 0)
+    worst, w, n_state, bound = certify_outputs(o, inputs_of(case), lin, kw, case.N, case.id, c_d, c_jc,
+                                               qp=lambda b: qp_of(case, lin, b))
+    if require:
+        assert pol.sum() >= 2 and 2 * pol.sum() >= ok.sum(), (case.id, "coverage", int(pol.sum()), int(ok.sum()))
+        assert not state_bounded(kw) or n_state >= min_state, (case.id, "coverage: state rows with a multiplier", n_state)
+    return worst, w, n_state, bound
+
+
+# the closed loop under a speed cap (tests/test_gpu_parity.py SBC "vcap", its workload: spline paths, seed 5): the
+# states the loop itself drives against the cap
+VCAP = dict(x_lo=[-np.inf, -np.inf, -np.inf, 0.2, -np.inf, -np.inf], x_hi=[np.inf, np.inf, np.inf, 1.3, np.inf, np.inf])
+VCAP_LOOP = dict(N=20, Ts=0.05, B=8, T=8, seed=5)
+
+
+def certify_visited(O, step, X, U, u0, window, vr, polish_mode, c_d=C_D, c_jc=C_JC):
+    """The VCAP_LOOP closed loop's visited states X [B,T+1,6] with applied commands U [B,T,2]: at every step t the
+    step entry `step(x, u_prev, path_ref, vref) -> outputs` on the state the loop stood in, its window from
+    `window(x positions) -> [B,N+1,3]`; the polished outputs certified on the oracle's linearization at that state.
+    Coverage, summed over the steps: polished on at least half of the solved (step, instance) pairs and on two; two with a state row carrying a
+    multiplier.  Returns (worst gap, Worst, solved, polished, with state rows)."""
+    N, Ts, T = VCAP_LOOP["N"], VCAP_LOOP["Ts"], VCAP_LOOP["T"]
+    w, worst, n_ok, n_pol, n_state = Worst(), -np.inf, 0, 0, 0
+    for t in range(T):
+        xt, ut = X[:, t], (U[:, t - 1] if t > 0 else u0)
+        prt = window(xt[:, 0])
+        o = step(xt, ut, prt, vr)
+        lin = Q.linearization(O, xt, ut, N, Ts)
+        g, wc, ns, _ = certify_outputs(o, (xt, ut, prt, vr), lin, VCAP, N, f"vcap mode {polish_mode} t={t}", c_d, c_jc)
+        worst = max(worst, g)
+        w.merge(wc)
+        n_ok += int((o["status"] <= 1).sum())
+        n_pol += int(((o["status"] <= 1) & (o["polished"] > 0)).sum())
+        n_state += ns
+    assert n_pol >= 2 and 2 * n_pol >= n_ok and n_state >= 2, ("vcap coverage", polish_mode, n_ok, n_pol, n_state)
+    return worst, w, n_ok, n_pol, n_state

@@ -5,6 +5,13 @@ the equality constraints force (:186-192), the objective (:224-250) and the dist
 rows (:195-221).  Whatever a solver returns as X_opt / objective for its own U_opt can be checked against these with
 no second solver in between.
 
+Optimality needs no solver either.  ``condensed`` eliminates the states (X = X_free + G u) and returns the QP as
+J(u) = 1/2 u' P u + q' u + c0, lo <= A u <= hi -- box, rate and state rows; P is positive definite because R, Rd > 0.
+``dual_bound`` evaluates the Lagrange dual d(y) = min_u L(u, y) in closed form: weak duality makes d(y) <= J* for
+every y >= 0, whatever produced y.  ``certificate`` guesses y for a given point from the point's own active rows (a
+least-squares fit of the stationarity condition, wrong-signed rows dropped) -- a heuristic, not a solver: a bad guess
+only makes d smaller, never invalid.  A point with J(u) - d(y) <= tol is thereby PROVED optimal to tol.
+
 ``rollout`` and ``cost`` return, beside their value, its abs-sum scale -- the same expression evaluated on absolute
 values, i.e. the size of the terms a float64 evaluation rounds (the idiom of tests/_knet_ref.py).  An error bar
 proportional to it follows the growth of the unstable plant at Ts = 0.05 instead of being one flat number.
@@ -89,6 +96,120 @@ def violation(U, u_prev, kw=None, X=None):
         state = outside(X, lo[:, None], hi[:, None])
         scale = max(scale, np.abs(X).max())
     return box, rate, state, float(scale)
+
+
+def _blocks(M2, N):
+    """blockdiag(M2, ..., M2), N times."""
+    return np.kron(np.eye(N), M2)
+
+
+def condensed(x0, Ad, Bd, g, u_prev, path_ref, vref, kw=None):
+    """The same QP with the states eliminated: P, q, c0, A, lo, hi, n_state with J(U) = 1/2 u' P u + q' u + c0 and
+    lo <= A u <= hi, u stage-major (u[2k + ch] = U[ch, k]).  X(U) = X_free + G u: X_free is rollout at U = 0 and
+    G [N+1, 6, 2N] follows the stage recurrence G_{k+1} = Ad[k] G_k, + Bd[k] in the columns of stage k.  The residual
+    rows of `cost` (lateral, heading, speed at k = 0..N) are affine in u; the input terms take the symmetric parts of
+    R and Rd with dU_0 = U_0 - u_prev.  Rows of A: the box on U, the rate rows D u (the u_prev offset moved into
+    lo / hi), then one row per (bounded state i -- either side finite --, stage k = 1..N): G[k, i] against
+    x_lo[i] - X_free[i, k] and x_hi[i] - X_free[i, k].  n_state counts those last rows."""
+    Ad, Bd, g = (np.asarray(a, dtype=np.float64) for a in (Ad, Bd, g))
+    N = Ad.shape[0]
+    n = 2 * N
+    up = np.asarray(u_prev, dtype=np.float64).reshape(2)
+    Xf, _ = rollout(x0, Ad, Bd, g, np.zeros((2, N)))
+    G = np.zeros((N + 1, 6, n))
+    for k in range(N):
+        G[k + 1] = Ad[k] @ G[k]
+        G[k + 1][:, 2 * k:2 * k + 2] += Bd[k]
+    pr = np.asarray(path_ref, dtype=np.float64)
+    vr = np.asarray(vref, dtype=np.float64).reshape(N + 1)
+    q_c, q_phi, q_vx = (float(_kw(kw, k)) for k in ("q_c", "q_phi", "q_vx"))
+    R = np.asarray(_kw(kw, "R"), dtype=np.float64).reshape(2, 2)
+    Rd = np.asarray(_kw(kw, "Rd"), dtype=np.float64).reshape(2, 2)
+    s, c = np.sin(pr[:, 2])[:, None], np.cos(pr[:, 2])[:, None]
+    # residual = M u + r0, weights w
+    M = np.concatenate([s * G[:, 0] - c * G[:, 1], G[:, 2], G[:, 3]])
+    r0 = np.concatenate([s[:, 0] * (Xf[0] - pr[:, 0]) - c[:, 0] * (Xf[1] - pr[:, 1]), Xf[2] - pr[:, 2], Xf[3] - vr])
+    w = np.repeat([q_c, q_phi, q_vx], N + 1)
+    D = np.eye(n) - np.eye(n, k=-2)                            # dU = D u + d0
+    d0 = np.zeros(n)
+    d0[:2] = -up
+    Rs, Rds = _blocks((R + R.T) / 2, N), _blocks((Rd + Rd.T) / 2, N)
+    P = 2.0 * (M.T @ (w[:, None] * M) + Rs + D.T @ Rds @ D)
+    q = 2.0 * (M.T @ (w * r0) + D.T @ (Rds @ d0))
+    c0 = float(np.sum(w * r0 * r0) + d0 @ Rds @ d0)
+    ub = np.asarray(_kw(kw, "u_bounds"), dtype=np.float64)        # [2, (lo, hi)]
+    db = np.asarray(_kw(kw, "du_bounds"), dtype=np.float64)
+    A = [np.eye(n), D]
+    lo = [np.tile(ub[:, 0], N), np.tile(db[:, 0], N) - d0]
+    hi = [np.tile(ub[:, 1], N), np.tile(db[:, 1], N) - d0]
+    x_lo, x_hi = _kw(kw, "x_lo"), _kw(kw, "x_hi")
+    xl = np.full(6, -np.inf) if x_lo is None else np.asarray(x_lo, dtype=np.float64).reshape(6)
+    xh = np.full(6, np.inf) if x_hi is None else np.asarray(x_hi, dtype=np.float64).reshape(6)
+    n_state = 0
+    for i in np.where(np.isfinite(xl) | np.isfinite(xh))[0]:
+        A.append(G[1:, i])
+        lo.append(xl[i] - Xf[i, 1:])
+        hi.append(xh[i] - Xf[i, 1:])
+        n_state += N
+    return P, q, c0, np.concatenate(A), np.concatenate(lo), np.concatenate(hi), n_state
+
+
+def objective(P, q, c0, u):
+    return float(0.5 * u @ P @ u + q @ u + c0)
+
+
+def stage_major(U):
+    """U [2,N] -> u [2N], u[2k + ch] = U[ch, k]."""
+    return np.asarray(U, dtype=np.float64).T.reshape(-1)
+
+
+def dual_bound(P, q, c0, A, lo, hi, y_plus, y_minus, scale=False):
+    """Weak duality: for ANY y_plus, y_minus >= 0 (taken only on finite hi / lo, negative parts dropped) and
+    v = q + A' (y_plus - y_minus), d = c0 - 1/2 v' P^-1 v - hi . y_plus + lo . y_minus = min_u L(u, y) <= J(u) at
+    every feasible u.  How y was found does not enter.  scale: return (d, its abs-sum scale) -- with w = P^-1 v,
+    |c0| + 1/2 |w|' |P| |w| + |hi| . y_plus + |lo| . y_minus: a backward-stable solve returns (P + E)^-1 v with |E| a
+    rounding multiple of |P|, which moves v' P^-1 v by w' E w to first order."""
+    yp = np.where(np.isfinite(hi), np.maximum(y_plus, 0.0), 0.0)
+    ym = np.where(np.isfinite(lo), np.maximum(y_minus, 0.0), 0.0)
+    v = q + A.T @ (yp - ym)
+    w = np.linalg.solve(P, v)
+    bh, bl = np.where(yp > 0, hi, 0.0) * yp, np.where(ym > 0, lo, 0.0) * ym
+    d = float(c0 - 0.5 * v @ w - np.sum(bh) + np.sum(bl))
+    if not scale:
+        return d
+    aw = np.abs(w)
+    return d, float(abs(c0) + 0.5 * aw @ np.abs(P) @ aw + np.sum(np.abs(bh)) + np.sum(np.abs(bl)))
+
+
+def certificate(P, q, c0, A, lo, hi, u, n_state=0):
+    """Multipliers for the point u from its own active set, and the dual bound they give.  Rows at a bound
+    (|A u - bound| <= 1e-7 (1 + |bound|)) are candidates; lam = lstsq(A_act', -(P u + q)); rows whose multiplier has
+    the wrong sign (lam < 0 at hi, > 0 at lo) are dropped; at most 20 rounds; what is left is clipped to the right
+    sign.  The iteration need not be right for the bound to be: whatever y comes out, d <= J*.  Returns
+    dict(J, d, d_scale: dual_bound's scale, y_plus, y_minus, n_state_active: state rows (the last n_state) carrying a
+    positive multiplier)."""
+    r = A @ u
+    m = len(r)
+    at_hi = np.isfinite(hi) & (np.abs(r - hi) <= 1e-7 * (1.0 + np.abs(hi)))
+    at_lo = np.isfinite(lo) & (np.abs(r - lo) <= 1e-7 * (1.0 + np.abs(lo)))
+    act = at_hi | at_lo
+    grad = P @ u + q
+    lam = np.zeros(m)
+    for _ in range(20):
+        lam[:] = 0.0
+        idx = np.where(act)[0]
+        if len(idx) == 0:
+            break
+        lam[idx] = np.linalg.lstsq(A[idx].T, -grad, rcond=None)[0]
+        wrong = act & (((lam < 0) & ~at_lo) | ((lam > 0) & ~at_hi))
+        if not wrong.any():
+            break
+        act &= ~wrong
+    yp = np.where(at_hi, np.maximum(lam, 0.0), 0.0)
+    ym = np.where(at_lo, np.maximum(-lam, 0.0), 0.0)
+    ns = int(((yp + ym)[m - n_state:] > 0).sum()) if n_state else 0
+    d, da = dual_bound(P, q, c0, A, lo, hi, yp, ym, scale=True)
+    return dict(J=objective(P, q, c0, u), d=d, d_scale=da, y_plus=yp, y_minus=ym, n_state_active=ns)
 
 
 def linearization(O, x0, u_prev, N, Ts, p=None):

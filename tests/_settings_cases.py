@@ -13,8 +13,9 @@ selects ("solve": mpc_solve.h, "split": mpc_split.h, "long": mpc_long.h, "genera
 horizons that still select it.  TABLE lists, per (case, row), the polish modes the GPU test runs: those in which
 the oracle with the row's settings departs from the oracle at defaults by more than tests/_mpc_checks.py parity
 allows (the discrimination rule), with at least two solved instances.  POLISHED lists the (case, row, mode) in which
-polished points are held to the 1e-9 violation bar and, without state bounds, to the 1e-7 optimality gap: those where
-the oracle alone meets both with the coverage condition.  Elsewhere polished points are held to the unpolished bar.
+polished points are held to the 1e-9 violation bar, to the weak-duality certificate and, without state bounds, to the
+1e-7 optimality gap against the IPM: those where the oracle alone meets them with the coverage condition.  Elsewhere
+polished points are held to the unpolished bar.
 """
 from __future__ import annotations
 
@@ -122,6 +123,10 @@ def candidates():
 # by tests/test_settings_ref.py on the CPU (X 0.170: N = 12, scaling_iters = 0; objective 0.102: N = 12, polish = 0)
 C_X_SET = 0.69
 C_J_SET = 0.41
+# (the certificate's constants C_D / C_JC of tests/_mpc_checks.py cover this table too: the same survey measures them)
+# (case, row) whose polished points, the oracle's own, have no state row with a multiplier: under max_iter = 60 only
+# the instances the bounds leave alone converge.  Their certificate is asserted without that coverage condition
+NO_STATE_ROWS = {("general-step-general_sb-N20-Ts0.02-vx", "cap_60")}
 # (row, text) without a discriminating case.  The three cap purposes are each one setting read at several horizons:
 # max_iter = 60 leaves the long horizons one solved instance (cap_400 is their cap row; it shows nothing new on the
 # general solver's N = 20, where cap_60 stands); 10 iterations reach status 1 only at N = 8 (cap_nocheck is the row
@@ -180,6 +185,11 @@ def unrefined(sc, row, mode):
     0 / 3 / 1 / 0 / 2 / 2 of the oracle's 1 / 4 / 5 / 5 / 5 / 4) with the same iteration counts; one refinement step
     removes the difference.  Asserted instead: the kernel polishes only where the oracle does."""
     return row == "refine_0" and mode == 0 and sc.text != "general"
+
+
+def min_state(sc, row):
+    """check_certificate's coverage: the instances that must carry a multiplier on a state row."""
+    return 0 if (sc.id, row) in NO_STATE_ROWS else 2
 
 
 def polished_modes(sc, row):

@@ -1,5 +1,6 @@
 """X_opt, objective and the optimum of every MPC solver tier against the QP itself (tests/_qp_ref.py: plain numpy, no
-solver) and against the oracle's sparse-form Riccati IPM (another algorithm).
+solver): optimality by a weak-duality certificate, state rows included, and against the oracle's sparse-form Riccati
+IPM (another algorithm) where there are none.
 
 mpc_step has five hand-written solvers, each with its own output epilogue (X_opt by the linear model, the cost of
 mpc_6stati.py:224-250, the scatter into [B,2,N] / [B,6,N+1]): the one-wave register kernel (N <= 20), the two-wave
@@ -13,9 +14,14 @@ oracle's worst error-over-bar ratio) and where the seeds are shown to meet the c
 A (QP entry point, the linearization is the test's): on EVERY instance with status <= 1, X_opt = rollout(U_opt)
 elementwise, objective = cost(X_opt, U_opt), u_cmd = U_opt[:, 0] and X_opt[:, 0] = x0 bitwise, the inequality rows
 to 1e-9 (polished) or OSQP's eps criterion; status > 1: NaN outputs and u_cmd = u_prev; polished points within 1e-7
-of the IPM's optimum (coverage: at least half of the solved instances and two).
+of the IPM's optimum (coverage: at least half of the solved instances and two) and, with or without state rows,
+certified to 1e-7 by a dual bound (tests/_mpc_checks.py certify_point; state-bound rows -- a vx band, vx + vy + omega,
+omega, vy, a one-sided heading bound -- in both modes, with two instances whose state rows carry multipliers, and
+parity with the oracle beside it).
 B (step entry point, the linearization is the kernel's): objective, feasibility and contract as in A; X_opt against the
-oracle's on all stages where both polished, 1e-5 (1 + |X|) -- 10 x the U bar, the ratio of test_oracle_golden.py.
+oracle's on all stages where both polished, 1e-5 (1 + |X|) -- 10 x the U bar, the ratio of test_oracle_golden.py; the
+certificate on the oracle's linearization.  The speed-capped closed loop: the step entry's polished outputs certified
+on every state 8 steps of the loop visit.
 C: both with non-default weights (off-diagonal R / Rd), asymmetric boxes, q_* and vehicle parameters, plus parity with
 the oracle under the same settings; a non-symmetric R gives the symmetrized R's outputs bit for bit.
 D: batch independence and determinism past N = 20 (row-split, long, general).
@@ -23,7 +29,10 @@ E: every tier's entry points on a workspace of exactly the size their query retu
 
 Measured on an MI355X, worst error / bar with C = 1 (the CPU oracle's in brackets): X 0.108 (0.108), objective 0.152
 (0.0847), violation 0.94 of the eps bar / 0.018 of 1e-9, optimality gap 5.0e-10, step-entry X_opt against the oracle's
-8.5e-9.  Most of the file's time is the N = 300 row: the general solver takes about 6 s per call at 600 variables.
+8.5e-9; certificate gap 5.0e-10 (5.0e-10) over the table, 7.6e-11 (7.6e-11) on state-bound rows and 5.1e-11 (4.3e-15) on
+the closed loop's 39 polished steps, 37 of them with active state rows; its lower side 0.0157 (0.0148) of the C = 1
+bar, the condensed objective 0.0462 (0.0462).  Most of the file's time is the N = 300 row: the general solver takes
+about 6 s per call at 600 variables.
 """
 import contextlib
 
@@ -88,12 +97,21 @@ def _parity(g, r, case, mode):
     return both
 
 
+def _certificate(o, case, lin, mode, sb, w):
+    """check_certificate in the modes of case.gap (state-bound rows: both), its ratios merged into w; the survey text."""
+    if not sb and mode not in case.gap:
+        return ""
+    cg, wc, n_state, _ = M.check_certificate(o, case, lin)
+    w.merge(wc)
+    return f", certificate gap {cg:.2e}" + (f", state rows with a multiplier on {n_state}" if sb else "")
+
+
 @pytest.mark.parametrize("case", M.QP_CASES + M.NONDEFAULT_CASES, ids=lambda c: c.id)
 def test_qp_entry_outputs_vs_qp(gpu, oracle_lib, case):
     """A (and C): traj_mpc_qp_batch on the oracle's linearization, both polish modes, every check on every instance."""
     x0, up, pr, vr = M.inputs(case.N, case.Ts, case.B, case.seed)
     lin = M.lin_of(oracle_lib, case)
-    sb = "x_lo" in M.SETTINGS[case.settings][0]
+    sb = M.state_bounded(M.SETTINGS[case.settings][0])
     for mode in (0, 1):
         cfg, par = _cfg(case, mode)
         with _route(case):
@@ -102,17 +120,19 @@ def test_qp_entry_outputs_vs_qp(gpu, oracle_lib, case):
             assert o["status"][1] == 3                       # the infeasible row: the epilogue's NaN / fallback branch
         w = M.check_outputs(o, case, lin)
         gap = None if sb or mode not in case.gap else M.check_gap(oracle_lib, o, case, lin)
-        if case.settings != "default" and not sb:
+        cert = _certificate(o, case, lin, mode, sb, w)
+        if case.settings != "default":
             _parity(o, M.oracle_step(oracle_lib, case, mode), case, mode)
         ok = o["status"] <= 1
         print(f"gpu qp {case.id} mode {mode}: solved {ok.sum()}/{case.B}, polished {(ok & (o['polished'] > 0)).sum()}, "
-              f"worst error / bar (C = 1): {w}" + ("" if gap is None else f", worst gap {gap:.2e}"))
+              f"worst error / bar (C = 1): {w}" + ("" if gap is None else f", worst gap {gap:.2e}") + cert)
 
 
 @pytest.mark.parametrize("case", M.STEP_CASES + M.NONDEFAULT_CASES, ids=lambda c: c.id)
 def test_step_entry_outputs_vs_qp_and_oracle(gpu, oracle_lib, case):
     """B (and C): traj_mpc_step_batch, the linearization inside the kernel."""
     x0, up, pr, vr = M.inputs(case.N, case.Ts, case.B, case.seed)
+    sb = M.state_bounded(M.SETTINGS[case.settings][0])
     for mode in (0, 1):
         cfg, par = _cfg(case, mode)
         with _route(case):
@@ -120,6 +140,9 @@ def test_step_entry_outputs_vs_qp_and_oracle(gpu, oracle_lib, case):
         if case.B >= 4:
             assert o["status"][1] == 3
         w = M.check_outputs(o, case, None)
+        # (the oracle's linearization stands for the kernel's, as check_gap takes it for the settings rows' step
+        # outputs: the 1e-7 bar absorbs the difference)
+        cert = _certificate(o, case, M.lin_of(oracle_lib, case), mode, sb, w)
         r = M.oracle_step(oracle_lib, case, mode)
         both = _parity(o, r, case, mode)
         if mode in case.gap:
@@ -127,7 +150,38 @@ def test_step_entry_outputs_vs_qp_and_oracle(gpu, oracle_lib, case):
         dx = np.abs(o["X_opt"][both] - r["X_opt"][both]) / (1.0 + np.abs(r["X_opt"][both]))
         assert dx.max(initial=0.0) <= 1e-5, (case.id, mode, dx.max())
         print(f"gpu step {case.id} mode {mode}: solved {(o['status'] <= 1).sum()}/{case.B}, both polished {both.sum()}, "
-              f"worst error / bar (C = 1): {w}, X vs oracle {dx.max(initial=0.0):.2e}")
+              f"worst error / bar (C = 1): {w}, X vs oracle {dx.max(initial=0.0):.2e}" + cert)
+
+
+def test_closed_loop_vcap_visited_states_certified(gpu, oracle_lib):
+    """The bounded closed loop's own steps: 8 steps of the speed-capped loop (tests/_mpc_checks.py VCAP_LOOP) and, on
+    every state it visits, the step entry's polished outputs proved optimal by the certificate -- the states the loop
+    itself drives against the cap.  The loop applied exactly those steps' u_cmd (bit for bit, as
+    tests/test_gpu_parity.py test_closed_loop_state_bounds_per_step holds at greater length)."""
+    from trajectory_generation_amd.workload import make_workload
+    L = M.VCAP_LOOP
+    N, Ts, B, T = L["N"], L["Ts"], L["B"], L["T"]
+    w = make_workload(B, N, Ts, kind="spline", seed=L["seed"])
+    paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
+    vr = np.tile(w["vref"], (B, 1))
+    for mode in (0, 1):
+        cfg = TB.config_struct(N=N, Ts=Ts, warm_start=0, polish_mode=mode, **M.VCAP)
+        res = TB.run_closed_loop(w["x0"], w["u0"], paths, w["vref"], T, cfg)
+        X, U, S = (res[k].cpu().numpy() for k in ("X", "U", "status"))
+        t_seen = []
+
+        def step(x, u, pr, v):
+            o = _np(TB.mpc_step_batch(x, u, pr, v, cfg))
+            t = len(t_seen)
+            t_seen.append(t)
+            assert np.array_equal(o["u_cmd"], U[:, t]) and np.array_equal(o["status"], S[t]), (mode, t)
+            return o
+
+        g, wc, n_ok, n_pol, n_state = M.certify_visited(
+            oracle_lib, step, X, U, np.asarray(w["u0"]).reshape(-1, 2),
+            lambda xs: TB.ref_window_batch(paths, xs, vr, N, Ts).cpu().numpy(), vr, mode)
+        print(f"gpu closed loop vcap mode {mode}: solved {n_ok}/{B * T}, polished {n_pol}, state rows with a multiplier on "
+              f"{n_state}, certificate gap {g:.2e}, worst error / bar (C = 1): {wc}")
 
 
 @pytest.mark.parametrize("case", M.NONDEFAULT_CASES, ids=lambda c: c.id)

@@ -8,7 +8,7 @@ another in its place or hard-codes the default fails (a).
 
 (a) traj_mpc_step_batch (traj_mpc_qp_batch on the oracle's linearization for the QP-entry case) against the QP
     (tests/_mpc_checks.py check_outputs with the row's own eps bars and the settings constants C_X_SET / C_J_SET,
-    check_gap where POLISHED lists the combination) and against the oracle with the same settings (parity: statuses
+    check_gap -- without state rows -- and check_certificate where POLISHED lists the combination) and against the oracle with the same settings (parity: statuses
     identical, iteration counts and polish outcomes equal on more than half of the row's solved instances and, pooled
     over the rows of one case and mode, on the fraction the default-settings parity tests demand; |dU_opt| <= 1e-6
     where both polished; the NaN / u_prev contract on unsolved instances).
@@ -20,7 +20,8 @@ in OSQP mode the K^-1 kernels polish only a subset of the oracle's instances.
 
 Measured on an MI355X, worst error / bar with C = 1 (the CPU oracle's in brackets): X 0.100 on the QP-entry case
 (0.170 over all cases), objective 0.083 (0.102), violation 0.999 of the row's eps bar (0.999) and 0.153 of 1e-9
-(0.153), optimality gap 1.5e-9.  Pooled agreement with the oracle: 100 % except iteration counts at N = 41 exact
+(0.153), optimality gap 1.5e-9, certificate gap 1.5e-9 (1.5e-9; general solver's rows 3.0e-11 (3.0e-11)), its lower
+side 0.0137 (0.0148) and the condensed objective 0.0418 (0.0462) of their C = 1 bars.  Pooled agreement with the oracle: 100 % except iteration counts at N = 41 exact
 mode (99.5 %), N = 65 exact mode (92.8 %, floor 90 %) and N = 129 OSQP mode (96.9 %, floor 95 %).  The file runs in
 under half a minute; no timing is measured or asserted here.
 """
@@ -103,11 +104,15 @@ def _run(O, sc, rname, mode):
     if (o["status"] <= 1).any() or (r["status"] <= 1).any():
         w = M.check_outputs(o, case, lin if sc.entry == "qp" else None, c_x=S.C_X_SET, c_j=S.C_J_SET, solver=kw,
                             polished_bar=listed)
-    gap = None
-    if listed and "x_lo" not in ckw:
-        gap = M.check_gap(O, o, case, lin)
+    gap = cert = None
+    if listed:
+        if not M.state_bounded(ckw):
+            gap = M.check_gap(O, o, case, lin)
+        cert = M.check_certificate(o, case, lin, min_state=S.min_state(sc, rname))
+        w.merge(cert[1])
     stats = M.parity(o, r, tag, up=up, polish_subset=S.unrefined(sc, rname, mode))
-    print(f"gpu {tag}: worst error / bar (C = 1): {w}" + ("" if gap is None else f", worst gap {gap:.2e}"))
+    print(f"gpu {tag}: worst error / bar (C = 1): {w}" + ("" if gap is None else f", worst gap {gap:.2e}")
+          + ("" if cert is None else f", certificate gap {cert[0]:.2e}, state rows with a multiplier on {cert[2]}"))
     _RUNS[key] = stats, w
     return _RUNS[key]
 

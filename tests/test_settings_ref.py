@@ -6,7 +6,9 @@ For every (case, row, polish mode) that tests/test_mpc_settings_gpu.py runs, wit
     in the "hinf" case, the one infeasible along the horizon;
   * every output check of tests/_mpc_checks.py check_outputs at a quarter of the settings constants C_X_SET / C_J_SET,
     with the row's own eps bars; where POLISHED lists the combination, the 1e-9 bar, the coverage condition (polished
-    on at least half, and two, of the solved instances) and, without state bounds, the 1e-7 optimality gap;
+    on at least half, and two, of the solved instances), without state bounds the 1e-7 optimality gap against the
+    IPM, and with or without them the weak-duality certificate (tests/_mpc_checks.py check_certificate: with state
+    bounds, two instances whose state rows carry multipliers);
   * discrimination: parity(oracle at defaults, oracle with the row) raises -- a kernel that ignores the setting
     computes the defaults' outputs and so fails the GPU test.  A row's value set back to its default makes this fail;
   * every row survives on at least one case of each kernel text, in at least one mode (PARITY_ONLY lists the rest);
@@ -19,7 +21,10 @@ Run with -s for the per-row survey: the discrimination reason and the worst erro
 Measured here (float64, x86-64), the oracle over the settings table, both polish modes: X 0.170 (N = 12,
 scaling_iters = 0), objective 0.102 (N = 12, polish = 0), violation 0.999 of the row's eps bar (unpolished; N = 65,
 check_interval = 1) and 0.153 of 1e-9 (polished, where listed); worst asserted optimality gap 1.5e-9.  C_X_SET = 0.69 and
-C_J_SET = 0.41 are 4 x the first two.
+C_J_SET = 0.41 are 4 x the first two.  The certificate where listed: gap 1.5e-9 (N = 49, delta = 1e-3; the general solver's
+rows 3.0e-11), lower side 0.0148 of the C = 1 bar (N = 20, Ts = 0.05, combined), condensed objective 0.0462 (N = 8) --
+tests/_mpc_checks.py's C_D = 0.06 and C_JC = 0.19 are 4 x these; one (case, row) has no state row with a multiplier on
+its polished points (_settings_cases.py NO_STATE_ROWS: max_iter = 60 on the general solver).
 
 What the survey left out of the table, with what was tried:
   * scaling_iters = 3 and 2 discriminate on one case each below N = 129 (1 is in the table); sigma = 1e-2 and 0.1 move
@@ -48,7 +53,8 @@ from tests import _settings_cases as S
 def evaluate(O, sc, rname, mode, polished_bar=None):
     """One (case, row, mode) with the oracle: dict(solved, polished, status, reason: why parity(defaults, row) raises
     or None, polished_ok: the 1e-9 bar, the coverage and the gap all hold, worst: the Worst ratios under the bar
-    the table assigns (polished_bar; None: the one polished_ok allows))."""
+    the table assigns (polished_bar; None: the one polished_ok allows), cert: check_certificate's return at a quarter
+    of C_D / C_JC with its coverage, state rows included -- part of polished_ok)."""
     case, row = sc.case, sc.row(rname)
     kw = M.SETTINGS[case.settings][0]
     lin = M.lin_of(O, case)
@@ -62,20 +68,24 @@ def evaluate(O, sc, rname, mode, polished_bar=None):
     except AssertionError as e:
         reason = e.args[0][1]
     polished_ok = bool(pol.sum() >= 2 and 2 * pol.sum() >= ok.sum())
-    gap = None
+    gap = cert = None
     if polished_ok:
         try:
             M.check_outputs(o, case, lin, c_x=S.C_X_SET / 4, c_j=S.C_J_SET / 4, nan_contract=False, solver=row[1])
-            if "x_lo" not in kw:
+            if not M.state_bounded(kw):
                 gap = M.check_gap(O, o, case, lin)
+            cert = M.check_certificate(o, case, lin, c_d=M.C_D / 4, c_jc=M.C_JC / 4,
+                                       min_state=S.min_state(sc, rname))
         except AssertionError:
             polished_ok = False
     if polished_bar is None:
         polished_bar = polished_ok
     worst = M.check_outputs(o, case, lin, c_x=S.C_X_SET / 4, c_j=S.C_J_SET / 4, nan_contract=False, solver=row[1],
                             polished_bar=polished_bar) if ok.any() else M.Worst()
+    if polished_ok and polished_bar:
+        worst.merge(cert[1])
     return dict(solved=int(ok.sum()), polished=int(pol.sum()), status=o["status"], reason=reason,
-                polished_ok=polished_ok, worst=worst, gap=gap)
+                polished_ok=polished_ok, worst=worst, gap=gap, cert=cert)
 
 
 def cap_margin_ok(O, sc, rname, mode):
@@ -144,6 +154,8 @@ def test_settings_table_with_oracle(oracle_lib, sc):
                     assert d["status"][2] == 3 and d["iters"][2] > 0 and d["iters"][1] == 0, tag
                 assert e["reason"] is not None, (tag, "the row does not discriminate")
                 assert not listed or e["polished_ok"], (tag, "listed for the polished bar / the gap")
+                if listed and (sc.id, rname) in S.NO_STATE_ROWS:
+                    assert e["cert"][2] < 2, (tag, "listed as without state-row coverage, but has it")
                 cap = ""
                 if rname.startswith("cap_"):
                     assert cap_margin_ok(O, sc, rname, mode), (tag, "a residual within 10 % of eps at the cap")
@@ -152,7 +164,9 @@ def test_settings_table_with_oracle(oracle_lib, sc):
                 print(f"oracle {sc.id} {rname} mode {mode}: solved {e['solved']}/{sc.case.B}, polished {e['polished']}"
                       f"{' (1e-9 bar + gap)' if listed else ''}, discriminates by {e['reason']}{cap}, "
                       f"worst error / bar (C = 1): {e['worst']}"
-                      + (f", worst gap {e['gap']:.2e}" if listed and e["gap"] is not None else ""))
+                      + (f", worst gap {e['gap']:.2e}" if listed and e["gap"] is not None else "")
+                      + (f", certificate gap {e['cert'][0]:.2e}, state rows with a multiplier on {e['cert'][2]}"
+                         if listed else ""))
     print(f"oracle {sc.id}: worst error / bar (C = 1) over its rows: {total}")
     # (check_outputs asserted 4 x worst <= C_X_SET / C_J_SET on every instance)
 
