@@ -249,6 +249,34 @@ int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c,
  * same workspace (a run clears the flag when it starts). */
 int traj_closed_loop_check(const void* workspace, size_t workspace_bytes, int B, int N, void* stream);
 
+/* ---- the evaluation after the loop (MPC/main.py:107-121; csrc/closed_stats.hip) ----
+ * traj_closed_loop_stats reads finished histories (hist_x / hist_u as the closed loop wrote them) and leaves, per
+ * trajectory and series, the record (n, mean, M2, min, max) over steps t = 0 .. T-1, 1 <= T <= hist_T:
+ *   d, delta          hist_u[b,t,:] (main.py:110-111);
+ *   dd, ddelta        hist_u[b,t,:] - hist_u[b,t-1,:], with u0[b] (u_prev before step 0) for t-1 = -1;
+ *   e_c, e_phi, e_v   the stage-0 terms of the step's cost at the post-step state x = hist_x[b,t+1,:] against the first
+ *                     point of the window from x (X* = X, Y* = y(X), phi* = atan(y'(X)), traj_ref_window_batch's):
+ *                     e_c = sin(phi*)(X-X*) - cos(phi*)(Y-Y*) (mpc_6stati.py:111-117), e_phi = atan2(sin(phi-phi*),
+ *                     cos(phi-phi*)), e_v = vx - vref[b,0].
+ * M2 is the sum of squared deviations from the mean (np.std's ddof = 0 is sqrt(M2 / n)).  A series with a non-finite
+ * sample has NaN in mean, M2, min and max; n stays the sample count.  fails[b] (may be NULL) = steps t < T whose
+ * status[t,b] is neither OPTIMAL nor OPTIMAL_INACCURATE, 0 with status NULL.
+ * traj_closed_loop_stats_pool merges the B records into pooled [7,5] (Chan's merge; merge order: the kept trajectories
+ * in index order, so pooling with a mask is pooling the kept rows alone) and adds up fails (either may be NULL);
+ * with nothing kept, n = 0 and the other fields are NaN.
+ * Both: DEVICE pointers, asynchronous on `stream`, no allocation, deterministic (the same bits on every launch).
+ * B == 0: TRAJ_OK, no launch.  TRAJ_E_ARG: B < 0, N < 1, T < 1, T > hist_T, or a missing pointer. */
+#define TRAJ_STATS_SERIES 7   /* d, delta, dd, ddelta, e_c, e_phi, e_v */
+#define TRAJ_STATS_FIELDS 5   /* n, mean, M2 (sum of squared deviations), min, max */
+int traj_closed_loop_stats(const traj_paths* paths, int B, int N, int T, int hist_T,
+                           const double* hist_x /*[B,hist_T+1,6]*/, const double* hist_u /*[B,hist_T,2]*/,
+                           const double* u0 /*[B,2]*/, const double* vref /*[B,N+1]*/,
+                           const int* status /*[>=T,B] or NULL*/, double* rec /*[B,7,5]*/, int* fails /*[B] or NULL*/,
+                           void* stream);
+int traj_closed_loop_stats_pool(int B, const double* rec /*[B,7,5]*/, const int* fails /*[B] or NULL*/,
+                                const unsigned char* mask /*[B] or NULL: 0 leaves a trajectory out*/,
+                                double* pooled /*[7,5]*/, long long* fails_total /*or NULL*/, void* stream);
+
 /* ---- dataset files (host memory) ----
  * traj_dataset_write_csv: the reference's CSV schema (generation_type1.py:139-158), written with nthreads
  * threads.  X [B,T+1,6] states, U [B,T,2] controls, noise [B,T+1,6] measurement noise (noisy file only),

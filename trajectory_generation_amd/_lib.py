@@ -165,6 +165,9 @@ _SIGS = {
     "traj_debug_split_min_n": (C.c_int, [C.c_int]),
     "traj_debug_set_item_stamps": (C.c_int, [_V]),
     "traj_closed_loop_check": (C.c_int, [_V, C.c_size_t, C.c_int, C.c_int, _V]),
+    "traj_closed_loop_stats": (C.c_int, [C.POINTER(Paths), C.c_int, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V, _V, _V,
+                                         _V, _V]),
+    "traj_closed_loop_stats_pool": (C.c_int, [C.c_int, _V, _V, _V, _V, _V, _V]),
     "traj_dataset_write_csv": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double, _V, _V, _V, _V,
                                          C.c_int]),
     "traj_dataset_format_f64_host": (C.c_int, [_V, C.c_longlong, _V, _V]),

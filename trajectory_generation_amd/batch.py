@@ -594,3 +594,202 @@ def run_closed_loop(x0, u0, paths: PathSet, vref, T, cfg: MpcConfig, params=None
         for t in range(T):
             closed_loop_step(x, u, paths, vr, cfg, params, t, hx, hu, st[t], it[t])
     return dict(X=hx, U=hu, status=st, iters=it, x=x, u=u)
+
+
+# ---------------------------------------------------------------- the evaluation after the loop (MPC/main.py:107-121)
+
+STATS_SERIES = ("d", "delta", "dd", "ddelta", "e_c", "e_phi", "e_v")   # TRAJ_STATS_SERIES
+STATS_FIELDS = ("n", "mean", "M2", "min", "max")                       # TRAJ_STATS_FIELDS
+_N, _MEAN, _M2, _MIN, _MAX = range(5)
+
+
+def stats_views(pooled) -> dict:
+    """The named views of a [7,5] record: n, mean, std = sqrt(M2 / n) (numpy's ddof = 0), min, max, each a dict keyed
+    by series name."""
+    pooled = np.asarray(pooled, dtype=np.float64).reshape(len(STATS_SERIES), len(STATS_FIELDS))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        std = np.sqrt(pooled[:, _M2] / pooled[:, _N])
+    cols = dict(n=pooled[:, _N], mean=pooled[:, _MEAN], std=std, min=pooled[:, _MIN], max=pooled[:, _MAX])
+    return {k: {s: float(v[i]) for i, s in enumerate(STATS_SERIES)} for k, v in cols.items()}
+
+
+def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None) -> dict:
+    """MPC/main.py:107-121 for a finished run (what run_closed_loop returns, recorded), on the device: the statistics of
+    d and delta, of their rates and of the three tracking errors over steps 0 .. T-1 (default: all recorded steps),
+    per trajectory and pooled (traj_closed_loop_stats, traj_closed_loop_stats_pool; the series: include/trajmpc.h).
+
+    u0 [B,2]: u_prev before step 0 (the u0 run_closed_loop took); vref as run_closed_loop takes it; mask [B] (bool or
+    0 / 1): False leaves a trajectory out of the pooled record.
+    Returns per_traj [B,7,5] and fails [B] (device tensors), pooled [7,5] (numpy: n, mean, M2, min, max per series),
+    fails_total (int) and the views of stats_views(pooled).  The read-back of pooled and the count (one copy of 288
+    bytes) is the only synchronisation."""
+    X, U = run["X"], run["U"]
+    if X is None or U is None:
+        raise ValueError("closed_loop_stats needs the recorded histories (run_closed_loop(record=True))")
+    X = _dev(X, None, X.device if torch.is_tensor(X) and X.is_cuda else None)
+    dev = X.device
+    U = _dev(U, None, dev)
+    B, hist_T = U.shape[0], U.shape[1]
+    if U.dim() != 3 or U.shape[2] != 2 or tuple(X.shape) != (B, hist_T + 1, 6):
+        raise ValueError(f"X must be [B,T+1,6] and U [B,T,2], got {tuple(X.shape)}, {tuple(U.shape)}")
+    T = hist_T if T is None else int(T)
+    if paths.B != B:
+        raise ValueError(f"paths holds {paths.B} trajectories, the run {B}")
+    if B > 0 and not 1 <= T <= hist_T:
+        raise ValueError(f"T = {T}: the statistics take 1 .. {hist_T} of the {hist_T} recorded steps")
+    u0 = _dev(u0, (B, 2), dev)
+    vr = _dev(vref, None, dev)
+    vr = vr.reshape(-1, vr.shape[-1])
+    if vr.shape[0] == 1 and B > 1:
+        vr = vr.expand(B, vr.shape[1]).contiguous()
+    if vr.shape[0] != B:
+        raise ValueError(f"vref must be [N+1] or [B,N+1] with B = {B}, got {tuple(vr.shape)}")
+    N = vr.shape[1] - 1
+    st = run.get("status")
+    if st is not None:
+        st = torch.as_tensor(st).to(device=dev, dtype=torch.int32).contiguous()
+        if st.dim() != 2 or st.shape[0] < T or st.shape[1] != B:
+            raise ValueError(f"status must be [>=T,B] = [>={T},{B}], got {tuple(st.shape)}")
+    rec = torch.empty((B, len(STATS_SERIES), len(STATS_FIELDS)), dtype=torch.float64, device=dev)
+    fails = torch.empty(B, dtype=torch.int32, device=dev)
+    ps = paths.struct()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().traj_closed_loop_stats(C.byref(ps), B, N, T, hist_T, _p(X), _p(U), _p(u0), _p(vr),
+                                                     _p(st), _p(rec), _p(fails), _stream()),
+                   "traj_closed_loop_stats")
+    pooled, fails_total = pool_stats(rec, fails, mask)
+    return dict(per_traj=rec, fails=fails, pooled=pooled, fails_total=fails_total, **stats_views(pooled))
+
+
+def pool_stats(per_traj, fails=None, mask=None) -> tuple:
+    """The records per_traj [B,7,5] of the trajectories mask keeps (default: all) merged into one on the device
+    (traj_closed_loop_stats_pool), with the sum of their fails [B] (default: 0).  Returns (pooled [7,5] numpy,
+    fails_total int): one copy of 288 bytes, which synchronises.  Nothing kept: n = 0, the other fields NaN."""
+    S, F = len(STATS_SERIES), len(STATS_FIELDS)
+    rec = _dev(per_traj, (-1, S, F), per_traj.device if torch.is_tensor(per_traj) and per_traj.is_cuda else None)
+    B, dev = rec.shape[0], rec.device
+    if fails is not None:
+        fails = torch.as_tensor(fails).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+    if mask is not None:
+        mask = torch.as_tensor(mask).to(device=dev).reshape(B).to(torch.uint8).contiguous()
+    if B == 0:     # no launch
+        pooled = np.full((S, F), np.nan)
+        pooled[:, _N] = 0.0
+        return pooled, 0
+    out = torch.empty(S * F + 1, dtype=torch.int64, device=dev)   # the pooled record's bits, then the count
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().traj_closed_loop_stats_pool(
+            B, _p(rec), _p(fails), _p(mask), _p(out), C.c_void_p(out.data_ptr() + 8 * S * F), _stream()),
+            "traj_closed_loop_stats_pool")
+    host = out.cpu().numpy()
+    return host[:S * F].view(np.float64).reshape(S, F).copy(), int(host[S * F])
+
+
+def path_fn_host(kinds, pcs, knots=None):
+    """The reference geometry of PathSet.build's arguments as the host specification's path function:
+    path_fn(b, xs) -> (y(xs), atan(y'(xs))) for an array xs, in numpy (path_eval's rule, workload.spline_eval's)."""
+    kinds = np.asarray(kinds)
+    pcs = np.asarray(pcs, dtype=np.float64).reshape(len(kinds), 4)
+    coefs = {b: spline_natural(*knots[b]) for b in range(len(kinds)) if kinds[b] == 2}
+
+    def path_fn(b, xs):
+        xs = np.asarray(xs, dtype=np.float64)
+        c = pcs[b]
+        if kinds[b] == 0:
+            return c[0] + xs * (c[1] + xs * (c[2] + xs * c[3])), np.arctan(c[1] + xs * (2.0 * c[2] + xs * 3.0 * c[3]))
+        if kinds[b] == 1:
+            a = c[1] * xs + c[2]
+            return c[0] * np.sin(a) + c[3], np.arctan(c[0] * c[1] * np.cos(a))
+        xk, cf = np.asarray(knots[b][0], dtype=np.float64), coefs[b]
+        nk = len(xk)
+        j = np.clip(np.searchsorted(xk, xs, side="right") - 1, 0, nk - 2)
+        q = cf[j]
+        t = xs - xk[j]
+        y = q[:, 0] + t * (q[:, 1] + t * (q[:, 2] + t * q[:, 3]))
+        dy = q[:, 1] + t * (2.0 * q[:, 2] + t * 3.0 * q[:, 3])
+        lo, hi = xs <= xk[0], xs >= xk[-1]
+        h = xk[-1] - xk[-2]
+        qe = cf[nk - 2]
+        ye = qe[0] + h * (qe[1] + h * (qe[2] + h * qe[3]))
+        se = qe[1] + h * (2.0 * qe[2] + h * 3.0 * qe[3])
+        y = np.where(lo, cf[0, 0] + cf[0, 1] * (xs - xk[0]), np.where(hi, ye + se * (xs - xk[-1]), y))
+        dy = np.where(lo, cf[0, 1], np.where(hi, se, dy))
+        return y, np.arctan(dy)
+
+    return path_fn
+
+
+def closed_loop_series_host(X, U, u0, path_fn, vref0) -> np.ndarray:
+    """The seven series of closed_loop_stats as numpy arrays [B,7,T]: X [B,T+1,6], U [B,T,2], u0 [B,2];
+    path_fn(b, xs [T]) -> (Y* [T], phi* [T]), the path's ordinate and heading at abscissae xs; vref0 [B] or a scalar,
+    the first entry of each trajectory's speed reference."""
+    X, U = np.asarray(X, dtype=np.float64), np.asarray(U, dtype=np.float64)
+    B, T = U.shape[0], U.shape[1]
+    u0 = np.asarray(u0, dtype=np.float64).reshape(B, 2)
+    v0 = np.broadcast_to(np.asarray(vref0, dtype=np.float64), (B,))
+    ser = np.empty((B, len(STATS_SERIES), T))
+    ser[:, 0:2] = U.transpose(0, 2, 1)
+    ser[:, 2:4] = (U - np.concatenate([u0[:, None, :], U[:, :-1]], axis=1)).transpose(0, 2, 1)
+    for b in range(B):
+        x = X[b, 1:T + 1]
+        ys, phis = path_fn(b, x[:, 0])
+        ys, phis = np.asarray(ys, dtype=np.float64), np.asarray(phis, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            ser[b, 4] = np.sin(phis) * (x[:, 0] - x[:, 0]) - np.cos(phis) * (x[:, 1] - ys)   # X* = X
+            ser[b, 5] = np.arctan2(np.sin(x[:, 2] - phis), np.cos(x[:, 2] - phis))
+        ser[b, 6] = x[:, 3] - v0[b]
+    return ser
+
+
+def _record_host(v) -> np.ndarray:
+    """(n, mean, M2, min, max) of the samples v by numpy's own reductions; NaN past n if one is not finite."""
+    v = np.asarray(v, dtype=np.float64).ravel()
+    if v.size == 0:
+        return np.array([0.0, np.nan, np.nan, np.nan, np.nan])
+    if not np.isfinite(v).all():
+        return np.array([float(v.size), np.nan, np.nan, np.nan, np.nan])
+    return np.array([float(v.size), np.mean(v), np.std(v) ** 2 * v.size, np.min(v), np.max(v)])
+
+
+def closed_loop_stats_host(X, U, u0, path_fn, vref0, status=None, mask=None) -> dict:
+    """The numpy specification of closed_loop_stats (arguments: closed_loop_series_host; status [>=T,B] or None): plain
+    np.mean / np.std / np.min / np.max per series, per trajectory and over the kept trajectories' samples together;
+    a series with a non-finite sample gets NaN in mean, M2, min and max, as on the device.
+    Returns numpy per_traj [B,7,5], fails [B], pooled [7,5], fails_total, series [B,7,T] and stats_views(pooled)."""
+    ser = closed_loop_series_host(X, U, u0, path_fn, vref0)
+    B, S, T = ser.shape
+    keep = np.ones(B, dtype=bool) if mask is None else np.asarray(mask).reshape(B).astype(bool)
+    per = np.array([[_record_host(ser[b, s]) for s in range(S)] for b in range(B)]).reshape(B, S, len(STATS_FIELDS))
+    pooled = np.array([_record_host(ser[keep, s]) for s in range(S)])
+    if status is None:
+        fails = np.zeros(B, dtype=np.int64)
+    else:
+        fails = (np.asarray(status)[:T] >= 2).sum(axis=0).astype(np.int64)
+    return dict(per_traj=per, fails=fails, pooled=pooled, fails_total=int(fails[keep].sum()), series=ser,
+                **stats_views(pooled))
+
+
+def merge_stats(a, b) -> np.ndarray:
+    """Chan's merge of two records [7,5] (or [...,7,5], broadcast): the record of the two sample sets together, in
+    float64.  n, min and max are exact; a side with n = 0 leaves the other unchanged; NaN fields stay NaN.  How
+    launches, shards and ranks combine their pooled records."""
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+    na, nb = a[..., _N], b[..., _N]
+    n = na + nb
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = nb / n
+        delta = b[..., _MEAN] - a[..., _MEAN]
+        out = np.stack([n, a[..., _MEAN] + delta * w, (a[..., _M2] + b[..., _M2]) + (delta * delta) * (na * w),
+                        np.minimum(a[..., _MIN], b[..., _MIN]), np.maximum(a[..., _MAX], b[..., _MAX])], axis=-1)
+    out = np.where((nb == 0)[..., None], a, out)
+    return np.where(((na == 0) & (nb != 0))[..., None], b, out)
+
+
+def mpc_stats(pooled) -> dict:
+    """The four numbers generation_type1 takes as `stats` (generation_type1.py:250's mpc_stats) from a pooled record
+    [7,5], or from what closed_loop_stats returns."""
+    if isinstance(pooled, dict):
+        pooled = pooled["pooled"]
+    v = stats_views(pooled)
+    return {"d_mean": v["mean"]["d"], "d_std": v["std"]["d"], "delta_mean": v["mean"]["delta"],
+            "delta_std": v["std"]["delta"]}

@@ -28,7 +28,7 @@ from .csv_write import (DEVICE_CSV_ROW_MAX, DEVICE_CSV_SLAB_BYTES, FMT_F64_MAX, 
                         write_csv, write_csv_device)
 from .generate import (_write_with_sidecar, _write_xu, gather_to_root, generate, generate_open_loop,  # noqa: F401
                        generate_piecewise, merge_datasets, pack_history, status_summary, unpack_history,
-                       write_status_csv)
+                       write_stats_json, write_status_csv)
 from .loader import _load_device, _load_native, load_vehicle_dataset  # noqa: F401
 from .noise import (NOISE_TIE_MARGIN, measurement_noise_device, measurement_noise_host, noise_device_raw,  # noqa: F401
                     noise_sigma, noise_tails_host)

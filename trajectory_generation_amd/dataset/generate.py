@@ -103,7 +103,7 @@ def _run_rank(run, B, out_prefix, dist, shards, write):
 
 def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=None, polish_mode=0,
              closed_loop=None, drop_failed=False, shards=False, device_csv=False, device_noise=False,
-             device_workload=False):
+             device_workload=False, stats=False):
     """Run the closed loop for this rank's B trajectories (ids rank * B .. rank * B + B - 1), gather the
     histories to rank 0 and (rank 0) write ``{out_prefix}_clean.csv`` / ``{out_prefix}_noisy.csv`` and the
     status sidecar ``{out_prefix}_status.csv`` (write_status_csv).
@@ -127,6 +127,12 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
       PathSet are built on the GPU in one launch (workload.make_workload_device: the same draws; Y, phi and the spline
       coefficients to rounding, so the trajectories are not the host-built workload's bit for bit).  closed_loop gets
       that dict: device tensors, knots=None, the PathSet under "paths".
+    stats: opt-in (default False: every output as without it, byte for byte) -- ``{out_prefix}_stats.json`` beside the
+      status sidecar (write_stats_json): the closed loop's statistics and tracking errors pooled over the written
+      trajectories (batch.closed_loop_stats on this rank's histories, on the GPU; drop_failed leaves the dropped ones
+      out), the four numbers generation_type1 takes as `stats`, and the failed steps.  With a process group every
+      rank's pooled record goes to rank 0 and is merged there in rank order (batch.merge_stats); shards: every rank
+      writes ``{out_prefix}_rank{r}_stats.json`` of its own share.
     Returns (X [W B,T+1,6], U [W B,T,2], status [T,W B]) on rank 0 and None on the other ranks (shards:
     this rank's (X, U, status) everywhere)."""
     from ..workload import make_workload, make_workload_device
@@ -140,12 +146,80 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
     if shards and drop_failed:
         raise ValueError("drop_failed re-indexes the whole dataset: it needs the gather (shards=False)")
 
+    pooled = []     # stats: this rank's (pooled record, failed steps)
+
     def run(id_offset):
-        res = closed_loop(build(B, N, Ts, kind=kind, seed=seed, id_offset=id_offset), T, cfg)
+        w = build(B, N, Ts, kind=kind, seed=seed, id_offset=id_offset)
+        if stats and w.get("paths") is None:
+            from .. import batch as TB
+            w["paths"] = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
+        res = closed_loop(w, T, cfg)
+        if stats:
+            pooled.append(_rank_stats(res, w, drop_failed))
         return res["X"], res["U"], res["status"]
 
-    return _run_rank(run, B, out_prefix, dist, shards, lambda prefix, X, U, st, ids: _write_with_sidecar(
+    out = _run_rank(run, B, out_prefix, dist, shards, lambda prefix, X, U, st, ids: _write_with_sidecar(
         prefix, X, U, st, ids, Ts, drop_failed, device_csv, device_noise))
+    if stats:
+        _write_rank_stats(pooled[0], out_prefix, dist, shards)
+    return out
+
+
+def _rank_stats(res, w, drop_failed):
+    """(pooled [7,5], fails_total) of one rank's closed loop res on its workload w; drop_failed: over the trajectories
+    without a failed step, the ones that are written."""
+    import torch
+
+    from .. import batch as TB
+    st = res["status"]
+    mask = None
+    if drop_failed:
+        mask = (torch.as_tensor(st) >= FAILED_STATUS).sum(dim=0) == 0
+    s = TB.closed_loop_stats(dict(X=res["X"], U=res["U"], status=st), w["paths"], w["vref"], w["u0"], mask=mask)
+    return s["pooled"], s["fails_total"]
+
+
+def _write_rank_stats(mine, out_prefix, dist, shards):
+    """The statistics' one collective: every rank's 36 numbers (the pooled record, the failed steps) gathered to rank
+    0 like the histories, merged there in rank order; shards: no gather, every rank writes its own."""
+    import torch
+
+    from .. import batch as TB
+    pooled, fails_total = mine
+    grouped = dist is not None and dist.is_initialized()
+    rank = dist.get_rank() if grouped else 0
+    if shards:
+        if out_prefix is not None:
+            write_stats_json(f"{out_prefix}_rank{rank}", pooled, fails_total)
+        return
+    if grouped:
+        dev = TB.require_gpu() if dist.get_backend() == "nccl" else torch.device("cpu")
+        row = torch.as_tensor(np.append(pooled.ravel(), float(fails_total)), dtype=torch.float64, device=dev)[None]
+        rows = gather_to_root(row, dist)
+        if rows is None:
+            return
+        rows = rows.cpu().numpy()
+        pooled, fails_total = rows[0, :-1].reshape(pooled.shape), int(rows[:, -1].sum())
+        for r in rows[1:]:
+            pooled = TB.merge_stats(pooled, r[:-1].reshape(pooled.shape))
+    if out_prefix is not None:
+        write_stats_json(out_prefix, pooled, fails_total)
+
+
+def write_stats_json(out_prefix, pooled, fails_total):
+    """``{out_prefix}_stats.json``: the pooled record by series name (n, mean, M2, min, max; floats as repr writes
+    them, so they read back to the bit), mpc_stats (batch.mpc_stats: generation_type1's `stats`) and fails_total."""
+    import json
+
+    from .. import batch as TB
+    pooled = np.asarray(pooled, dtype=np.float64)
+    doc = {"pooled": {s: {f: float(pooled[i, j]) for j, f in enumerate(TB.STATS_FIELDS)}
+                      for i, s in enumerate(TB.STATS_SERIES)},
+           "mpc_stats": TB.mpc_stats(pooled), "fails_total": int(fails_total)}
+    with open(f"{out_prefix}_stats.json", "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    return doc
 
 
 def _check_device_noise(device_csv, device_noise):
