@@ -241,6 +241,29 @@ int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c,
                          double* hist_x, double* hist_u, int* status, int* iters, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- a speed reference indexed by the loop's time (additive: the ABI version stays 4) ----
+ * The two entry points above read the same vref[b, 0..N] at every step, as main.py:87 rebuilds its profile inside the
+ * loop.  The _sched forms take a speed schedule S: row b at vref + vref_row * b (vref_row in doubles; 0 = one row
+ * shared by all B trajectories), vref_len entries long, and step t uses
+ *     vref_k = S[b, t * vref_step + k],  k = 0 .. N
+ * for the window's running sum X*_{k+1} = X*_k + vref_k Ts and for the q_vx cost rows -- bit for bit what
+ * traj_closed_loop_step gives when it is handed the contiguous copy S[:, t*vref_step : t*vref_step + N + 1] at step t.
+ * vref_step = 1: a schedule sampled every Ts; vref_step = 0: the same N + 1 entries every step, so (vref_row,
+ * vref_len, vref_step) = (N + 1, N + 1, 0) is traj_closed_loop_step / _run / _stats, which are exactly these calls.
+ * traj_closed_loop_stats_sched takes e_v at step t as vx(hist_x[b, t+1]) - S[b, (t + 1) * vref_step]: stage 0 of the
+ * window the next step starts from (vref[b, 0] when vref_step = 0).
+ * TRAJ_E_ARG, before any launch: vref_step not 0 or 1; vref_len < N + 1; vref_row neither 0 nor >= vref_len; the last
+ * entry the call reads at or past vref_len -- t * vref_step + N (step), (t0 + steps - 1) * vref_step + N (run),
+ * T * vref_step (stats).  Everything else as the functions they extend. */
+int traj_closed_loop_step_sched(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                                double* x, double* u_prev, const double* vref, long long vref_row, int vref_len,
+                                int vref_step, int t, int hist_T, double* hist_x, double* hist_u, int* status,
+                                int* iters, void* workspace, size_t workspace_bytes, void* stream);
+int traj_closed_loop_run_sched(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                               double* x, double* u_prev, const double* vref, long long vref_row, int vref_len,
+                               int vref_step, int t0, int steps, int hist_T, double* hist_x, double* hist_u,
+                               int* status, int* iters, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Synchronizes `stream` and reports whether the last traj_closed_loop_run on this workspace lost an
  * instance hand-off: a workgroup that waited for an instance's previous step longer than the spin
  * bound (traj_debug_spin_limit) went on with the state it found, so the run's x / u_prev / history
@@ -273,6 +296,13 @@ int traj_closed_loop_stats(const traj_paths* paths, int B, int N, int T, int his
                            const double* u0 /*[B,2]*/, const double* vref /*[B,N+1]*/,
                            const int* status /*[>=T,B] or NULL*/, double* rec /*[B,7,5]*/, int* fails /*[B] or NULL*/,
                            void* stream);
+/* (the speed schedule's form: see traj_closed_loop_step_sched) */
+int traj_closed_loop_stats_sched(const traj_paths* paths, int B, int N, int T, int hist_T,
+                                 const double* hist_x /*[B,hist_T+1,6]*/, const double* hist_u /*[B,hist_T,2]*/,
+                                 const double* u0 /*[B,2]*/, const double* vref /*row b at vref_row * b*/,
+                                 long long vref_row, int vref_len, int vref_step,
+                                 const int* status /*[>=T,B] or NULL*/, double* rec /*[B,7,5]*/,
+                                 int* fails /*[B] or NULL*/, void* stream);
 int traj_closed_loop_stats_pool(int B, const double* rec /*[B,7,5]*/, const int* fails /*[B] or NULL*/,
                                 const unsigned char* mask /*[B] or NULL: 0 leaves a trajectory out*/,
                                 double* pooled /*[7,5]*/, long long* fails_total /*or NULL*/, void* stream);

@@ -1,0 +1,120 @@
+"""What the speed schedule buys: a closed loop that follows v(t) in one fused launch, against the only way to run it
+without the schedule entry points -> profiles/vref_schedule_bench.json ("scheduled_run").
+
+  python tools/vref_schedule_bench.py [--B 4096] [--T 240] [--N 20] [--reps 5] [--json PATH]
+
+One process, the same inputs for both: workload.make_workload (spline paths) and the schedule S [B,T+N],
+S[b,j] = 1.5 + 0.5 sin(2 pi j Ts / 6 + b).  After one warm-up of each, the two alternate `reps` times:
+  fused      batch.run_closed_loop(vref_step=1): one traj_closed_loop_run_sched launch for all T steps (and the
+             hand-off check, which synchronises);
+  host_loop  T times from the host: batch.ref_window_batch on the state's X and the slice S[:, t : t + N + 1],
+             batch.mpc_step_batch, batch.f_cont_batch and the plant update in torch -- device tensors throughout, the
+             host only sequences the launches; one synchronise at the end.
+Both run warm_start = 0, so they compute the same thing: the histories are compared bit for bit.  A third figure,
+fused_warm, is the fused run as shipped (warm_start = 1).  Wall time per run; median, min, max.  Needs the GPU.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def spread(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "reps": len(xs)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=4096)
+    ap.add_argument("--T", type=int, default=240)
+    ap.add_argument("--N", type=int, default=20)
+    ap.add_argument("--Ts", type=float, default=0.05)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "vref_schedule_bench.json"))
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("vref_schedule_bench needs the GPU")
+    from trajectory_generation_amd import batch as TB
+    from trajectory_generation_amd.workload import make_workload
+    B, T, N, Ts = a.B, a.T, a.N, a.Ts
+    dev = TB.require_gpu()
+    w = make_workload(B, N, Ts, kind="spline", seed=0)
+    paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
+    S = 1.5 + 0.5 * np.sin(2 * np.pi * (np.arange(T + N)[None, :] * Ts) / 6.0 + np.arange(B)[:, None])
+    Sd, x0, u0 = TB._dev(S, None, dev), TB._dev(w["x0"], None, dev), TB._dev(w["u0"], None, dev)
+    cold, warm = TB.config_struct(N=N, Ts=Ts, warm_start=0), TB.config_struct(N=N, Ts=Ts)
+    sync = torch.cuda.synchronize
+
+    def fused(cfg=cold):
+        return TB.run_closed_loop(x0, u0, paths, Sd, T, cfg, vref_step=1)
+
+    out_buf = TB._outputs(B, N, dev)
+
+    def host_loop():
+        x, u = x0.clone(), u0.clone()
+        X = torch.empty((B, T + 1, 6), dtype=torch.float64, device=dev)
+        U = torch.empty((B, T, 2), dtype=torch.float64, device=dev)
+        st = torch.empty((T, B), dtype=torch.int32, device=dev)
+        X[:, 0] = x
+        for t in range(T):
+            win = Sd[:, t:t + N + 1].contiguous()
+            pr = TB.ref_window_batch(paths, x[:, 0].contiguous(), win, N, Ts)
+            o = TB.mpc_step_batch(x, u, pr, win, cold, out=out_buf)
+            u = o["u_cmd"].clone()
+            x = x + Ts * TB.f_cont_batch(x, u)
+            X[:, t + 1], U[:, t], st[t] = x, u, o["status"]
+        sync()
+        return dict(X=X, U=U, status=st)
+
+    res = {"fused_s": [], "host_loop_s": [], "fused_warm_s": []}
+    f = h = None
+    for rep in range(a.reps + 1):          # the first pass is the warm-up of each
+        for key, fn in (("fused_s", fused), ("host_loop_s", host_loop), ("fused_warm_s", lambda: fused(warm))):
+            sync()
+            t0 = time.perf_counter()
+            r = fn()
+            sync()
+            dt = time.perf_counter() - t0
+            if rep:
+                res[key].append(dt)
+            if key == "fused_s":
+                f = r
+            elif key == "host_loop_s":
+                h = r
+    same = lambda p, q: bool(((p == q) | (torch.isnan(p) & torch.isnan(q))).all())   # noqa: E731
+    out = {"what": "B trajectories, T closed-loop steps along a speed schedule [B,T+N] (vref_step = 1): one fused "
+                   "launch against T host-sequenced step calls on the same inputs, alternating, wall seconds per run",
+           "B": B, "T": T, "N": N, "Ts": Ts, "reps": a.reps, "device": torch.cuda.get_device_name(0)}
+    out.update({k: spread(v) for k, v in res.items()})
+    for k in ("fused_s", "host_loop_s", "fused_warm_s"):
+        out[k]["steps_per_s_at_median"] = B * T / out[k]["median"]
+    out["host_loop_over_fused_at_median"] = out["host_loop_s"]["median"] / out["fused_s"]["median"]
+    out["fused_faster_beyond_spread"] = bool(out["fused_s"]["max"] < out["host_loop_s"]["min"])
+    out["compare"] = {"X_equal": same(f["X"], h["X"]), "U_equal": same(f["U"], h["U"]),
+                      "status_equal": bool(torch.equal(f["status"], h["status"])),
+                      "failed_steps": int((f["status"] >= 2).sum())}
+    os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+    doc = {}
+    if os.path.exists(a.json):
+        with open(a.json) as fjs:
+            doc = json.load(fjs)
+    doc["scheduled_run"] = out
+    with open(a.json, "w") as fjs:
+        json.dump(doc, fjs, indent=1)
+        fjs.write("\n")
+    print(json.dumps(out, indent=1))
+    c = out["compare"]
+    if not (c["X_equal"] and c["U_equal"] and c["status_equal"]):
+        raise SystemExit("the fused scheduled run differs from the host-sequenced steps")
+
+
+if __name__ == "__main__":
+    main()

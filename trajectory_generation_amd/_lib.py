@@ -255,6 +255,15 @@ _SIGS = {
                                         _V, _V, _V, C.c_int, C.c_int, _V, _V, _V, _V, _V, C.c_size_t, _V]),
     "traj_closed_loop_run": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
                                         _V, _V, _V, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V, _V, C.c_size_t, _V]),
+    # the speed schedule's forms: vref_row, vref_len, vref_step after vref
+    "traj_closed_loop_step_sched": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
+                                              _V, _V, _V, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, _V, _V, _V,
+                                              _V, _V, C.c_size_t, _V]),
+    "traj_closed_loop_run_sched": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths), C.c_int,
+                                             _V, _V, _V, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _V,
+                                             _V, _V, _V, _V, C.c_size_t, _V]),
+    "traj_closed_loop_stats_sched": (C.c_int, [C.POINTER(Paths), C.c_int, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V,
+                                               C.c_longlong, C.c_int, C.c_int, _V, _V, _V, _V]),
 }
 
 _lib = None

@@ -540,48 +540,102 @@ def _closed_extra(B: int, cfg: MpcConfig) -> int:
     return max(0, need - int(L.traj_mpc_workspace_bytes(int(B), int(cfg.N))))
 
 
+def _schedule_shape(vref, B, vref_step, need, what):
+    """The speed schedule's checks, on shapes alone (no GPU): vref_step 0 or 1; with 1, vref [L] (one row for every
+    trajectory) or [B,L] with L >= need.  Returns (shared row?, L); raises ValueError."""
+    if vref_step not in (0, 1):
+        raise ValueError(f"{what}: vref_step must be 0 (the same window every step) or 1 (a schedule sampled at Ts), "
+                         f"got {vref_step!r}")
+    shape = tuple(np.shape(vref))
+    if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] != B):
+        raise ValueError(f"{what}: a speed schedule is [L] or [B,L] with B = {B}, got {shape}")
+    if shape[-1] < need:
+        raise ValueError(f"{what}: the schedule holds {shape[-1]} samples, the call reads {need}")
+    return len(shape) == 1, int(shape[-1])
+
+
+def _schedule_args(vref, B, dev, vref_step, need, what):
+    """(tensor, vref_row, vref_len, vref_step) of the _sched entry points for a schedule vref [L] or [B,L]: a 1-D
+    schedule goes as one shared row (vref_row = 0), never tiled."""
+    shared, L = _schedule_shape(vref, B, vref_step, need, what)
+    vr = _dev(vref, None, dev)
+    return vr, (0 if shared else L), L, int(vref_step)
+
+
 def closed_loop_step(x, u_prev, paths: PathSet, vref, cfg: MpcConfig, params=None, t=0, hist_x=None, hist_u=None,
-                     status=None, iters=None):
-    """One step of MPC/main.py:85-101 for all B trajectories; x [B,6], u_prev [B,2] updated in place."""
+                     status=None, iters=None, vref_step=0):
+    """One step of MPC/main.py:85-101 for all B trajectories; x [B,6], u_prev [B,2] updated in place.
+    vref_step=1: vref is a speed schedule [L] or [B,L], L >= t + N + 1, and this step reads vref[b, t + k], k = 0..N
+    (traj_closed_loop_step_sched); 0 (default): vref [B,N+1], the same at every step."""
     B = x.shape[0]
+    if vref_step != 0:
+        _schedule_shape(vref, B, vref_step, int(t) + cfg.N + 1, "closed_loop_step")
     ps = paths.struct()
     T = hist_u.shape[1] if hist_u is not None else 0
     ws = workspace(B, cfg.N, x.device, _closed_extra(B, cfg))
+    if vref_step != 0:
+        vr, row, L, vs = _schedule_args(vref, B, x.device, vref_step, int(t) + cfg.N + 1, "closed_loop_step")
+        _lib.check(_lib.lib().traj_closed_loop_step_sched(
+            C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vr), row, L, vs, int(t),
+            int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()),
+            "traj_closed_loop_step_sched")
+        return
     _lib.check(_lib.lib().traj_closed_loop_step(
         C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vref), int(t), int(T),
         _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()), "traj_closed_loop_step")
 
 
 def closed_loop_run(x, u_prev, paths: PathSet, vref, cfg: MpcConfig, params=None, t0=0, steps=1, hist_x=None,
-                    hist_u=None, status=None, iters=None, check=True):
+                    hist_u=None, status=None, iters=None, check=True, vref_step=0):
     """Steps t0 .. t0+steps-1 of MPC/main.py:85-101 in ONE fused launch (traj_closed_loop_run), bit-identical
     to `steps` closed_loop_step calls; x, u_prev updated in place; status / iters [steps, B].
-    check: synchronize and raise RuntimeError if the run lost an instance hand-off (traj_closed_loop_check)."""
+    check: synchronize and raise RuntimeError if the run lost an instance hand-off (traj_closed_loop_check).
+    vref_step=1: vref is a speed schedule [L] or [B,L], L >= t0 + steps + N, and step t reads vref[b, t + k], k = 0..N
+    (traj_closed_loop_run_sched: still one launch); 0 (default): vref [B,N+1], the same at every step."""
     B = x.shape[0]
+    if vref_step != 0:
+        _schedule_shape(vref, B, vref_step, int(t0) + int(steps) + cfg.N, "closed_loop_run")
     ps = paths.struct()
     T = hist_u.shape[1] if hist_u is not None else 0
     ws = workspace(B, cfg.N, x.device, _closed_extra(B, cfg))
-    _lib.check(_lib.lib().traj_closed_loop_run(
-        C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vref), int(t0),
-        int(steps), int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()),
-        "traj_closed_loop_run")
+    if vref_step != 0:
+        vr, row, L, vs = _schedule_args(vref, B, x.device, vref_step, int(t0) + int(steps) + cfg.N, "closed_loop_run")
+        _lib.check(_lib.lib().traj_closed_loop_run_sched(
+            C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vr), row, L, vs,
+            int(t0), int(steps), int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8,
+            _stream()), "traj_closed_loop_run_sched")
+    else:
+        _lib.check(_lib.lib().traj_closed_loop_run(
+            C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vref), int(t0),
+            int(steps), int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()),
+            "traj_closed_loop_run")
     if check:   # synchronizes: a lost instance hand-off raises instead of returning stale trajectories
         _lib.check(_lib.lib().traj_closed_loop_check(_p(ws), ws.numel() * 8, B, cfg.N, _stream()),
                    "traj_closed_loop_run")
 
 
-def run_closed_loop(x0, u0, paths: PathSet, vref, T, cfg: MpcConfig, params=None, record=True, fused=True) -> dict:
+def run_closed_loop(x0, u0, paths: PathSet, vref, T, cfg: MpcConfig, params=None, record=True, fused=True,
+                    vref_step=0) -> dict:
     """T closed-loop steps (MPC/main.py:85-101) for B trajectories, all on the device: one fused launch
     (closed_loop_run), or one launch sequence per step (fused=False; identical results).
 
+    vref_step=0 (default): vref [N+1] or [B,N+1], read anew at every step, as main.py:87 rebuilds its profile inside
+    the loop.  vref_step=1: vref is a speed schedule over the run, [L] (shared by all trajectories, passed as one row)
+    or [B,L] with L >= T + N, sampled at Ts: step t takes vref[b, t : t + N + 1] for its window and its q_vx rows.
     Returns X [B,T+1,6] (X[:,0] = x0), U [B,T,2], status [T,B], iters [T,B] (torch.cuda)."""
+    if vref_step != 0:
+        _schedule_shape(vref, int(np.shape(x0)[0]) if len(np.shape(x0)) == 2 else 1, vref_step, int(T) + cfg.N,
+                        "run_closed_loop")
     x = _dev(x0, (-1, 6)).clone()
     B = x.shape[0]
     dev = x.device
     u = _dev(u0, (B, 2), dev).clone()
-    vr = _dev(vref, (-1, cfg.N + 1), dev)
-    if vr.shape[0] == 1 and B > 1:
-        vr = vr.expand(B, cfg.N + 1).contiguous()
+    if vref_step != 0:
+        vr = _dev(vref, None, dev)
+    else:
+        vr = _dev(vref, (-1, cfg.N + 1), dev)
+        if vr.shape[0] == 1 and B > 1:
+            vr = vr.expand(B, cfg.N + 1).contiguous()
     hx = torch.empty((B, T + 1, 6), dtype=torch.float64, device=dev) if record else None
     hu = torch.empty((B, T, 2), dtype=torch.float64, device=dev) if record else None
     if record:
@@ -589,10 +643,10 @@ def run_closed_loop(x0, u0, paths: PathSet, vref, T, cfg: MpcConfig, params=None
     st = torch.empty((T, B), dtype=torch.int32, device=dev)
     it = torch.empty((T, B), dtype=torch.int32, device=dev)
     if fused:
-        closed_loop_run(x, u, paths, vr, cfg, params, 0, T, hx, hu, st, it)
+        closed_loop_run(x, u, paths, vr, cfg, params, 0, T, hx, hu, st, it, vref_step=vref_step)
     else:
         for t in range(T):
-            closed_loop_step(x, u, paths, vr, cfg, params, t, hx, hu, st[t], it[t])
+            closed_loop_step(x, u, paths, vr, cfg, params, t, hx, hu, st[t], it[t], vref_step=vref_step)
     return dict(X=hx, U=hu, status=st, iters=it, x=x, u=u)
 
 
@@ -613,19 +667,24 @@ def stats_views(pooled) -> dict:
     return {k: {s: float(v[i]) for i, s in enumerate(STATS_SERIES)} for k, v in cols.items()}
 
 
-def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None) -> dict:
+def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None, vref_step=0) -> dict:
     """MPC/main.py:107-121 for a finished run (what run_closed_loop returns, recorded), on the device: the statistics of
     d and delta, of their rates and of the three tracking errors over steps 0 .. T-1 (default: all recorded steps),
     per trajectory and pooled (traj_closed_loop_stats, traj_closed_loop_stats_pool; the series: include/trajmpc.h).
 
     u0 [B,2]: u_prev before step 0 (the u0 run_closed_loop took); vref as run_closed_loop takes it; mask [B] (bool or
     0 / 1): False leaves a trajectory out of the pooled record.
+    vref_step=1: vref is the run's speed schedule [L] or [B,L], L >= T + 1 (what run_closed_loop took), and e_v at step
+    t is vx(X[b,t+1]) - vref[b,t+1], the speed the next step's window starts from (traj_closed_loop_stats_sched).
     Returns per_traj [B,7,5] and fails [B] (device tensors), pooled [7,5] (numpy: n, mean, M2, min, max per series),
     fails_total (int) and the views of stats_views(pooled).  The read-back of pooled and the count (one copy of 288
     bytes) is the only synchronisation."""
     X, U = run["X"], run["U"]
     if X is None or U is None:
         raise ValueError("closed_loop_stats needs the recorded histories (run_closed_loop(record=True))")
+    if vref_step != 0:
+        hT = int(np.shape(U)[1])
+        _schedule_shape(vref, int(np.shape(U)[0]), vref_step, (hT if T is None else int(T)) + 1, "closed_loop_stats")
     X = _dev(X, None, X.device if torch.is_tensor(X) and X.is_cuda else None)
     dev = X.device
     U = _dev(U, None, dev)
@@ -639,12 +698,16 @@ def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None) -> dict:
         raise ValueError(f"T = {T}: the statistics take 1 .. {hist_T} of the {hist_T} recorded steps")
     u0 = _dev(u0, (B, 2), dev)
     vr = _dev(vref, None, dev)
-    vr = vr.reshape(-1, vr.shape[-1])
-    if vr.shape[0] == 1 and B > 1:
-        vr = vr.expand(B, vr.shape[1]).contiguous()
-    if vr.shape[0] != B:
-        raise ValueError(f"vref must be [N+1] or [B,N+1] with B = {B}, got {tuple(vr.shape)}")
-    N = vr.shape[1] - 1
+    if vref_step != 0:
+        # (the horizon only bounds the row's length: every N >= 1 with N + 1 <= L gives the same record)
+        row, L, N = (0 if vr.dim() == 1 else vr.shape[-1]), vr.shape[-1], 1
+    else:
+        vr = vr.reshape(-1, vr.shape[-1])
+        if vr.shape[0] == 1 and B > 1:
+            vr = vr.expand(B, vr.shape[1]).contiguous()
+        if vr.shape[0] != B:
+            raise ValueError(f"vref must be [N+1] or [B,N+1] with B = {B}, got {tuple(vr.shape)}")
+        N = vr.shape[1] - 1
     st = run.get("status")
     if st is not None:
         st = torch.as_tensor(st).to(device=dev, dtype=torch.int32).contiguous()
@@ -654,9 +717,14 @@ def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None) -> dict:
     fails = torch.empty(B, dtype=torch.int32, device=dev)
     ps = paths.struct()
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().traj_closed_loop_stats(C.byref(ps), B, N, T, hist_T, _p(X), _p(U), _p(u0), _p(vr),
-                                                     _p(st), _p(rec), _p(fails), _stream()),
-                   "traj_closed_loop_stats")
+        if vref_step != 0:
+            _lib.check(_lib.lib().traj_closed_loop_stats_sched(
+                C.byref(ps), B, N, T, hist_T, _p(X), _p(U), _p(u0), _p(vr), row, L, int(vref_step), _p(st), _p(rec),
+                _p(fails), _stream()), "traj_closed_loop_stats_sched")
+        else:
+            _lib.check(_lib.lib().traj_closed_loop_stats(C.byref(ps), B, N, T, hist_T, _p(X), _p(U), _p(u0), _p(vr),
+                                                         _p(st), _p(rec), _p(fails), _stream()),
+                       "traj_closed_loop_stats")
     pooled, fails_total = pool_stats(rec, fails, mask)
     return dict(per_traj=rec, fails=fails, pooled=pooled, fails_total=fails_total, **stats_views(pooled))
 
@@ -722,11 +790,17 @@ def path_fn_host(kinds, pcs, knots=None):
 def closed_loop_series_host(X, U, u0, path_fn, vref0) -> np.ndarray:
     """The seven series of closed_loop_stats as numpy arrays [B,7,T]: X [B,T+1,6], U [B,T,2], u0 [B,2];
     path_fn(b, xs [T]) -> (Y* [T], phi* [T]), the path's ordinate and heading at abscissae xs; vref0 [B] or a scalar,
-    the first entry of each trajectory's speed reference."""
+    the first entry of each trajectory's speed reference, or [B,T]: the speed e_v at step t is taken against, column
+    t (for a schedule S read with vref_step = 1 that is S[:, 1:T+1])."""
     X, U = np.asarray(X, dtype=np.float64), np.asarray(U, dtype=np.float64)
     B, T = U.shape[0], U.shape[1]
     u0 = np.asarray(u0, dtype=np.float64).reshape(B, 2)
-    v0 = np.broadcast_to(np.asarray(vref0, dtype=np.float64), (B,))
+    v0 = np.asarray(vref0, dtype=np.float64)
+    if v0.ndim == 2:
+        if v0.shape != (B, T):
+            raise ValueError(f"vref0 per step must be [B,T] = [{B},{T}], got {v0.shape}")
+    else:
+        v0 = np.broadcast_to(v0, (B,))
     ser = np.empty((B, len(STATS_SERIES), T))
     ser[:, 0:2] = U.transpose(0, 2, 1)
     ser[:, 2:4] = (U - np.concatenate([u0[:, None, :], U[:, :-1]], axis=1)).transpose(0, 2, 1)

@@ -7,7 +7,9 @@
 //       e_c, e_phi, e_v   the stage-0 terms of the controller's cost at the post-step state x = hist_x[b,t+1,:]
 //                     (main.py's traj_X): the window's first point X* = X, Y* = y(X), phi* = atan(y'(X)) by
 //                     path_eval / pm_atan as build_window (mpc_frame.h) forms it; e_c = lateral_error
-//                     (mpc_6stati.py:111-117), e_phi = atan2(sin(phi - phi*), cos(phi - phi*)), e_v = vx - vref[b,0]
+//                     (mpc_6stati.py:111-117), e_phi = atan2(sin(phi - phi*), cos(phi - phi*)), e_v = vx - vref[b,0];
+//                     with a speed schedule (traj_closed_loop_stats_sched, vref_step = 1) e_v = vx - S[b, t+1]: stage 0 of
+//                     the window the NEXT step starts from, as the other two errors are taken at that window's first point
 //   traj_closed_loop_stats_pool   the B records (those the mask keeps) merged into one
 //
 // One wave per trajectory, four per workgroup; lanes stride over t, each with Welford's update on its own samples;
@@ -82,16 +84,17 @@ __device__ __forceinline__ int st_wave_sum(int v) {
     return v;
 }
 
-__global__ __launch_bounds__(ST_BLOCK) void closed_stats_kernel(PathArgs pa, int B, int N, int T, int hist_T,
+__global__ __launch_bounds__(ST_BLOCK) void closed_stats_kernel(PathArgs pa, int B, int T, int hist_T,
                                                                 const double* hist_x, const double* hist_u,
                                                                 const double* u0, const double* vref,
+                                                                long long vref_row, int vref_step,
                                                                 const int* status, double* rec, int* fails) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * ST_WAVES + (threadIdx.x >> 6);
     if (b >= B) return;   // (the whole wave: nothing below synchronizes across waves)
     const double* hx = hist_x + (size_t)b * (hist_T + 1) * 6;
     const double* hu = hist_u + (size_t)b * hist_T * 2;
-    const double v0 = vref[(size_t)b * (N + 1)];
+    const double* vr = vref + (size_t)vref_row * b;
 
     double mean[ST_S], m2[ST_S], lo[ST_S], hi[ST_S];
     bool bad[ST_S];
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(ST_BLOCK) void closed_stats_kernel(PathArgs pa, int
         double se, ce;
         pm_sincos(x[2] - phis, &se, &ce);
         v[5] = pm_atan2(se, ce);
-        v[6] = x[3] - v0;
+        v[6] = x[3] - vr[(size_t)(t + 1) * vref_step];
         ++n;
         const double rn = 1.0 / (double)n;
 #pragma unroll
@@ -239,11 +242,10 @@ __global__ __launch_bounds__(ST_BLOCK) void closed_stats_pool_kernel(int B, cons
 
 }  // namespace tgmpc
 
-extern "C" {
-
-int traj_closed_loop_stats(const traj_paths* paths, int B, int N, int T, int hist_T, const double* hist_x,
-                           const double* hist_u, const double* u0, const double* vref, const int* status, double* rec,
-                           int* fails, void* stream) {
+// both statistics entry points: vref row b at vref + vref_row b, e_v at step t against its entry (t + 1) vref_step
+static int stats_launch(const traj_paths* paths, int B, int N, int T, int hist_T, const double* hist_x,
+                        const double* hist_u, const double* u0, const double* vref, long long vref_row, int vref_step,
+                        const int* status, double* rec, int* fails, void* stream) {
     using namespace tgmpc;
     if (B < 0 || N < 1 || T < 1 || T > hist_T) return TRAJ_E_ARG;
     if (!paths || !paths->kind || !paths->pc || (paths->kmax >= 2 && (!paths->nk || !paths->xk || !paths->coef)))
@@ -252,9 +254,30 @@ int traj_closed_loop_stats(const traj_paths* paths, int B, int N, int T, int his
     if (!hist_x || !hist_u || !u0 || !vref || !rec) return TRAJ_E_ARG;
     const PathArgs pa{paths->kmax, paths->kind, paths->pc, paths->nk, paths->xk, paths->coef};
     const unsigned grid = (unsigned)(((long long)B + ST_WAVES - 1) / ST_WAVES);
-    hipLaunchKernelGGL(closed_stats_kernel, dim3(grid), dim3(ST_BLOCK), 0, (hipStream_t)stream, pa, B, N, T, hist_T,
-                       hist_x, hist_u, u0, vref, status, rec, fails);
+    hipLaunchKernelGGL(closed_stats_kernel, dim3(grid), dim3(ST_BLOCK), 0, (hipStream_t)stream, pa, B, T, hist_T,
+                       hist_x, hist_u, u0, vref, vref_row, vref_step, status, rec, fails);
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+}
+
+extern "C" {
+
+int traj_closed_loop_stats_sched(const traj_paths* paths, int B, int N, int T, int hist_T, const double* hist_x,
+                                 const double* hist_u, const double* u0, const double* vref, long long vref_row,
+                                 int vref_len, int vref_step, const int* status, double* rec, int* fails,
+                                 void* stream) {
+    if ((vref_step != 0 && vref_step != 1) || (long long)vref_len < (long long)N + 1 ||
+        (vref_row != 0 && vref_row < vref_len) || (long long)T * vref_step >= (long long)vref_len)
+        return TRAJ_E_ARG;
+    return stats_launch(paths, B, N, T, hist_T, hist_x, hist_u, u0, vref, vref_row, vref_step, status, rec, fails,
+                        stream);
+}
+
+// (the plain [B,N+1] reference: the schedule entry point's (N + 1, N + 1, 0))
+int traj_closed_loop_stats(const traj_paths* paths, int B, int N, int T, int hist_T, const double* hist_x,
+                           const double* hist_u, const double* u0, const double* vref, const int* status, double* rec,
+                           int* fails, void* stream) {
+    return stats_launch(paths, B, N, T, hist_T, hist_x, hist_u, u0, vref, (long long)N + 1, 0, status, rec, fails,
+                        stream);
 }
 
 int traj_closed_loop_stats_pool(int B, const double* rec, const int* fails, const unsigned char* mask, double* pooled,

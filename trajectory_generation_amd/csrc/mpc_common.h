@@ -54,7 +54,7 @@ struct KArgs {
     const double* x0;        // [B,6]  (closed loop: state, updated in place)
     const double* u_prev;    // [B,2]
     const double* path_ref;  // [B,N+1,3] (unused in closed loop)
-    const double* vref;      // [B,N+1]
+    const double* vref;      // [B,N+1], or a speed schedule: row b at vref + vref_row b, read from vref_step * step on
     const double* Ad;        // [B,N,6,6] (QP-only mode)
     const double* Bd;
     const double* gd;
@@ -89,7 +89,14 @@ struct KArgs {
     int run_ahead;           // fused: a workgroup keeps its instance for the next step while that step is at most
                              //        run_ahead levels past the queue's draw front (0: every step from the queue)
     int wps;                 // fused: waves per SIMD of the kernel instance to launch (2, or 3 where built)
+    long long vref_row;      // vref's row stride in doubles (N + 1 for a plain [B,N+1]; 0: one row shared by all instances)
+    int vref_step;           // closed loop: entries the window advances along the row per step (0: the same N + 1 every step)
 };
+
+// vref of instance b at closed-loop step tstep (stages k = 0 .. N at [k]); the step and QP entry points pass tstep = 0
+__device__ __forceinline__ const double* vref_at(const KArgs& a, int b, int tstep) {
+    return a.vref + (size_t)a.vref_row * b + (size_t)a.vref_step * tstep;
+}
 
 // Fused closed loop: coherent (sc1) stores and loads of an instance's state handed between workgroups on any XCD
 // (mpc_solve.h explains the protocol)

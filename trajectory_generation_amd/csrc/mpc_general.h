@@ -379,7 +379,7 @@ __global__ __launch_bounds__(GEN_NT) void solve_gen_kernel(const KArgs a, double
     const double* x0 = a.x0 + 6 * (size_t)b;
     const double* up = a.u_prev + 2 * (size_t)b;
     const double* pref = a.path_ref + (size_t)3 * (N + 1) * b;
-    const double* vr = a.vref + (size_t)(N + 1) * b;
+    const double* vr = vref_at(a, b, a.t);
     const double* Adk = a.Ad + (size_t)36 * N * b;
     const double* Bdk = a.Bd + (size_t)12 * N * b;
     const double* gdk = a.gd + (size_t)6 * N * b;

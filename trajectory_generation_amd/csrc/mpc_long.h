@@ -103,7 +103,7 @@ __global__ __launch_bounds__(NT) void solve_long_kernel(const KArgs a, double* l
         }
         return m;
     };
-    const double* vr = a.vref + (size_t)(N + 1) * b;
+    const double* vr = vref_at(a, b, a.t);
     if constexpr (CLOSED) {
         load_state<true, false>(a, b, t, s_xc, s_uc);
         __syncthreads();

@@ -432,7 +432,11 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     for (int i = t; i < NEX; i += NT) s_ex[i] = 0.0;
     for (int i = t; i < NFS; i += NT) s_F[i] = 0.0;
     load_state<CLOSED, FUSED>(a, b, t, s_x0, s_up);
-    for (int i = t; i < N + 1; i += NT) s_vref[i] = a.vref[(size_t)(N + 1) * b + i];
+    {
+        // (the row's address from the uniform instance and step: scalar, none of it in the lanes' registers)
+        const double* vr = vref_at(a, __builtin_amdgcn_readfirstlane(b), __builtin_amdgcn_readfirstlane(tstep));
+        for (int i = t; i < N + 1; i += NT) s_vref[i] = vr[i];
+    }
     if (!CLOSED)
         for (int i = t; i < 3 * (N + 1); i += NT) s_pref[i] = a.path_ref[(size_t)3 * (N + 1) * b + i];
     __syncthreads();

@@ -177,7 +177,6 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
     const int N = c.N, n = 2 * N;
     const bool own = r < n;
     const int kk = r >> 1, ch = r & 1;
-    const double* vr = a.vref + (size_t)(N + 1) * b;
 
     // ---- block helpers ----
     int xb = 0, bb = 0;
@@ -259,6 +258,11 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
     };
 
     // ---- inputs (:144-163 normalisation by the caller; CLOSED: state, u_prev and the window) ----
+    // vref_k of the stages in LDS first (CLOSED: before the window's running sum, which reads it there; the row's
+    // address is not kept past this point)
+    const double* vr = vref_at(a, b, tstep);
+    if constexpr (CLOSED)
+        for (int k = t; k <= N; k += NT) s_vr[k] = vr[k];
     if constexpr (CLOSED) {
         if (FUSED) {   // the state the instance's previous step published (sc1 loads, mpc_solve.h st_coh / ld_coh)
             if (t < 6) s_xc[t] = ld_coh(a.x_state + 6 * (size_t)b + t);
@@ -272,7 +276,7 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
             double xs = s_xc[0];
             s_prc[0] = xs;
             for (int k = 0; k < N; ++k) {
-                xs = xs + vr[k] * c.Ts;
+                xs = xs + s_vr[k] * c.Ts;
                 s_prc[3 * (k + 1)] = xs;
             }
         }
@@ -296,7 +300,7 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
     // the stage loops' per-stage inputs that do not depend on the chain, in LDS before it starts: vref_k, and sin / cos
     // of phi*_k (one stage per thread, the same calls as in the loop)
     for (int k = t; k <= N; k += NT) {
-        s_vr[k] = vr[k];
+        if constexpr (!CLOSED) s_vr[k] = vr[k];
         if constexpr (!CLOSED) pm_sincos(pref[3 * k + 2], &s_sc[k][0], &s_sc[k][1]);
     }
     if (t == 0) { s_flag[0] = 0; s_flag[1] = 0; }
@@ -315,7 +319,7 @@ __global__ __launch_bounds__(SplitCfg<H>::NT) __attribute__((amdgpu_waves_per_eu
         if (t < 6) bad |= !isfinite(x0[t]);
         if (t < 2) bad |= !isfinite(up[t]);
         for (int i = t; i < 3 * (N + 1); i += NT) bad |= !isfinite(pref[i]);
-        for (int i = t; i < N + 1; i += NT) bad |= !isfinite(vr[i]);
+        for (int i = t; i < N + 1; i += NT) bad |= !isfinite(s_vr[i]);
         if (bad) s_flag[0] = 1;
     }
 

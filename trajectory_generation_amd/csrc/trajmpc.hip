@@ -117,14 +117,16 @@ __global__ void lateral_error_kernel(int B, const double* X, const double* Y, co
 }
 
 // main.py:51-68 batched (one thread per trajectory: the x-advance is a running sum)
-// (xs_stride: x_start[xs_stride b] -- 1 for traj_ref_window_batch, 6 for the closed loop's state rows)
+// (xs_stride: x_start[xs_stride b] -- 1 for traj_ref_window_batch, 6 for the closed loop's state rows; vref row b at
+// vref + vrow b + voff: N + 1 and 0 for a plain [B,N+1], the closed loop's schedule row and its step's offset)
 __global__ void ref_window_kernel(PathArgs pa, int B, int N, double Ts, const double* x_start, int xs_stride,
-                                  const double* vref, double* pref) {
+                                  const double* vref, long long vrow, long long voff, double* pref) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double xs = x_start[(size_t)xs_stride * b];
+    const double* vr = vref + (size_t)vrow * b + (size_t)voff;
     for (int k = 0; k <= N; ++k) {
-        if (k > 0) xs = xs + vref[(size_t)(N + 1) * b + k - 1] * Ts;
+        if (k > 0) xs = xs + vr[k - 1] * Ts;
         double y, dy;
         path_eval(pa, b, xs, y, dy);
         double* o = pref + ((size_t)(N + 1) * b + k) * 3;
@@ -532,6 +534,7 @@ static int mpc_common(const traj_vehicle_params* p, const traj_mpc_config* c, in
     a.c = *c;
     a.B = B;
     a.x0 = x0; a.u_prev = u_prev; a.path_ref = path_ref; a.vref = vref;
+    a.vref_row = c->N + 1;
     if (lin) {
         carve_workspace(a, ws, B, c->N);
         a.wsWarm = nullptr;
@@ -603,7 +606,7 @@ int traj_ref_window_batch(const traj_paths* paths, int B, int N, double Ts, cons
     if (!x_start || !vref || !path_ref) return TRAJ_E_ARG;
     PathArgs pa{paths->kmax, paths->kind, paths->pc, paths->nk, paths->xk, paths->coef};
     hipLaunchKernelGGL(ref_window_kernel, dim3(nblk(B, 128)), dim3(128), 0, (hipStream_t)stream, pa, B, N, Ts,
-                       x_start, 1, vref, path_ref);
+                       x_start, 1, vref, (long long)(N + 1), 0LL, path_ref);
     return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
 }
 
@@ -645,7 +648,7 @@ static int closed_step_sb(const KArgs& a0, const Route& r, void* ws, hipStream_t
     int* const sbuf = (int*)(uc + (size_t)B * 2);
     stamp(0, st);
     hipLaunchKernelGGL(ref_window_kernel, dim3(nblk(B, 128)), dim3(128), 0, st, a0.path, B, N, a0.c.Ts,
-                       (const double*)a0.x_state, 6, a0.vref, pr);
+                       (const double*)a0.x_state, 6, a0.vref, a0.vref_row, (long long)a0.vref_step * a0.t, pr);
     KArgs a = a0;
     a.x0 = a0.x_state;
     a.u_prev = a0.u_state;
@@ -668,14 +671,16 @@ static int closed_step_sb(const KArgs& a0, const Route& r, void* ws, hipStream_t
 
 // the closed-loop entry points' kernel arguments: the loop's state, the paths, the history and the carved workspace
 static KArgs closed_args(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
-                         double* x, double* u_prev, const double* vref, int t, int hist_T, double* hist_x,
-                         double* hist_u, int* status, int* iters, void* workspace) {
+                         double* x, double* u_prev, const double* vref, long long vref_row, int vref_step, int t,
+                         int hist_T, double* hist_x, double* hist_u, int* status, int* iters, void* workspace) {
     KArgs a;
     std::memset(&a, 0, sizeof(a));
     a.p = *p;
     a.c = *c;
     a.B = B;
     a.vref = vref;
+    a.vref_row = vref_row;
+    a.vref_step = vref_step;
     a.path = PathArgs{paths->kmax, paths->kind, paths->pc, paths->nk, paths->xk, paths->coef};
     a.x_state = x;
     a.u_state = u_prev;
@@ -690,18 +695,30 @@ static KArgs closed_args(const traj_vehicle_params* p, const traj_mpc_config* c,
     return a;
 }
 
-int traj_closed_loop_step(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
-                          double* x, double* u_prev, const double* vref, int t, int hist_T, double* hist_x,
-                          double* hist_u, int* status, int* iters, void* workspace, size_t workspace_bytes,
-                          void* stream) {
+// The speed schedule of the _sched entry points (include/trajmpc.h): what they refuse before any launch.  `last` is the
+// step whose window reaches furthest, last * vref_step + N the last element read.
+static bool sched_ok(int N, long long vref_row, int vref_len, int vref_step, long long last) {
+    if (vref_step != 0 && vref_step != 1) return false;
+    if (vref_len < N + 1) return false;
+    if (vref_row != 0 && vref_row < vref_len) return false;
+    return last < 0 || last * vref_step + N < (long long)vref_len;
+}
+
+int traj_closed_loop_step_sched(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                                double* x, double* u_prev, const double* vref, long long vref_row, int vref_len,
+                                int vref_step, int t, int hist_T, double* hist_x, double* hist_u, int* status,
+                                int* iters, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || B < 0 || !paths_ok(paths)) return TRAJ_E_ARG;
     const Route r = route(c, B, Entry::ClosedStep, switches());
     if (r.err) return r.err;
+    if (!sched_ok(c->N, vref_row, vref_len, vref_step, t)) return TRAJ_E_ARG;
     if (B == 0) return TRAJ_OK;
     if (!x || !u_prev || !vref) return TRAJ_E_ARG;
     if (!workspace || workspace_bytes < r.need) return TRAJ_E_ARG;
     if ((hist_x || hist_u) && (t < 0 || t >= hist_T)) return TRAJ_E_ARG;
-    KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, t, hist_T, hist_x, hist_u, status, iters, workspace);
+    if (vref_step && t < 0) return TRAJ_E_ARG;
+    KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, vref_row, vref_step, t, hist_T, hist_x, hist_u, status,
+                          iters, workspace);
     hipStream_t st = (hipStream_t)stream;
     switch (r.tier) {
         case Tier::General: return closed_step_sb(a, r, workspace, st);
@@ -727,18 +744,29 @@ int traj_closed_loop_step(const traj_vehicle_params* p, const traj_mpc_config* c
     return e;
 }
 
-int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
-                         double* x, double* u_prev, const double* vref, int t0, int steps, int hist_T,
-                         double* hist_x, double* hist_u, int* status, int* iters, void* workspace,
-                         size_t workspace_bytes, void* stream) {
+int traj_closed_loop_step(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                          double* x, double* u_prev, const double* vref, int t, int hist_T, double* hist_x,
+                          double* hist_u, int* status, int* iters, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    const int n1 = c ? c->N + 1 : 0;   // (a null configuration: the route's error, as before)
+    return traj_closed_loop_step_sched(p, c, paths, B, x, u_prev, vref, n1, n1, 0, t, hist_T, hist_x, hist_u, status,
+                                       iters, workspace, workspace_bytes, stream);
+}
+
+int traj_closed_loop_run_sched(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                               double* x, double* u_prev, const double* vref, long long vref_row, int vref_len,
+                               int vref_step, int t0, int steps, int hist_T, double* hist_x, double* hist_u,
+                               int* status, int* iters, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || B < 0 || steps < 0 || !paths_ok(paths)) return TRAJ_E_ARG;
     const Route r = route(c, B, Entry::ClosedRun, switches());
     if (r.err) return r.err;
+    if (!sched_ok(c->N, vref_row, vref_len, vref_step, steps > 0 ? (long long)t0 + steps - 1 : -1)) return TRAJ_E_ARG;
     if (B == 0 || steps == 0) return TRAJ_OK;
     if (!x || !u_prev || !vref || t0 < 0) return TRAJ_E_ARG;
     if (!workspace || workspace_bytes < r.need) return TRAJ_E_ARG;
     if ((hist_x || hist_u) && t0 + steps > hist_T) return TRAJ_E_ARG;
-    KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, t0, hist_T, hist_x, hist_u, status, iters, workspace);
+    KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, vref_row, vref_step, t0, hist_T, hist_x, hist_u, status,
+                          iters, workspace);
     a.nsteps = steps;
     a.fused_grid = g_fused_grid;
     // kernel instance: capacity 40, 2 waves per SIMD (3 from TRAJ_FUSED_W3_MIN_STEPS steps when that is set); capacity
@@ -804,6 +832,15 @@ int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c,
                                         : launch_mpc(a, st, 3);
     stamp_last(st);
     return e;
+}
+
+int traj_closed_loop_run(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
+                         double* x, double* u_prev, const double* vref, int t0, int steps, int hist_T,
+                         double* hist_x, double* hist_u, int* status, int* iters, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    const int n1 = c ? c->N + 1 : 0;
+    return traj_closed_loop_run_sched(p, c, paths, B, x, u_prev, vref, n1, n1, 0, t0, steps, hist_T, hist_x, hist_u,
+                                      status, iters, workspace, workspace_bytes, stream);
 }
 
 int traj_closed_loop_check(const void* workspace, size_t workspace_bytes, int B, int N, void* stream) {

@@ -78,7 +78,7 @@ def _closed_loop_gpu(w, T, cfg):
     paths = w.get("paths")      # make_workload_device built them with the workload
     if paths is None:
         paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
-    return TB.run_closed_loop(w["x0"], w["u0"], paths, w["vref"], T, cfg)
+    return TB.run_closed_loop(w["x0"], w["u0"], paths, w["vref"], T, cfg, vref_step=w.get("vref_step", 0))
 
 
 def _run_rank(run, B, out_prefix, dist, shards, write):
@@ -103,7 +103,7 @@ def _run_rank(run, B, out_prefix, dist, shards, write):
 
 def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=None, polish_mode=0,
              closed_loop=None, drop_failed=False, shards=False, device_csv=False, device_noise=False,
-             device_workload=False, stats=False):
+             device_workload=False, stats=False, speed_schedule=None):
     """Run the closed loop for this rank's B trajectories (ids rank * B .. rank * B + B - 1), gather the
     histories to rank 0 and (rank 0) write ``{out_prefix}_clean.csv`` / ``{out_prefix}_noisy.csv`` and the
     status sidecar ``{out_prefix}_status.csv`` (write_status_csv).
@@ -133,10 +133,20 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
       out), the four numbers generation_type1 takes as `stats`, and the failed steps.  With a process group every
       rank's pooled record goes to rank 0 and is merged there in rank order (batch.merge_stats); shards: every rank
       writes ``{out_prefix}_rank{r}_stats.json`` of its own share.
+    speed_schedule: None (default: every output as without it, byte for byte -- the workload's vref [B,N+1], the same
+      window at every step), or a speed reference over the whole run, one sample per Ts: an array [W B,T+N] (row i:
+      trajectory id i) or a callable (ids, T, N, Ts) -> [len(ids),T+N].  Each rank takes the rows of its ids; its
+      workload then carries vref [B,T+N] and vref_step = 1, step t reads vref[b, t : t + N + 1]
+      (batch.run_closed_loop(vref_step=1)), and the statistics' e_v is taken against the schedule.
     Returns (X [W B,T+1,6], U [W B,T,2], status [T,W B]) on rank 0 and None on the other ranks (shards:
     this rank's (X, U, status) everywhere)."""
     from ..workload import make_workload, make_workload_device
     _check_device_noise(device_csv, device_noise)
+    if speed_schedule is not None and not callable(speed_schedule):
+        speed_schedule = np.asarray(speed_schedule, dtype=np.float64)
+        if speed_schedule.ndim != 2 or speed_schedule.shape[1] != T + N:
+            raise ValueError(f"speed_schedule must be [W*B,T+N] = [*,{T + N}] (or a callable), got "
+                             f"{speed_schedule.shape}")
     build = make_workload_device if device_workload else make_workload
     cfg = None
     if closed_loop is None:
@@ -150,6 +160,8 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
 
     def run(id_offset):
         w = build(B, N, Ts, kind=kind, seed=seed, id_offset=id_offset)
+        if speed_schedule is not None:
+            w["vref"], w["vref_step"] = _rank_schedule(speed_schedule, id_offset, B, T, N, Ts), 1
         if stats and w.get("paths") is None:
             from .. import batch as TB
             w["paths"] = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
@@ -165,6 +177,21 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
     return out
 
 
+def _rank_schedule(speed_schedule, id_offset, B, T, N, Ts):
+    """The rows of generate's speed_schedule for the ids id_offset .. id_offset + B - 1, as float64 [B,T+N]."""
+    ids = np.arange(id_offset, id_offset + B)
+    if callable(speed_schedule):
+        rows = np.asarray(speed_schedule(ids, T, N, Ts), dtype=np.float64)
+    else:
+        if id_offset + B > speed_schedule.shape[0]:
+            raise ValueError(f"speed_schedule holds {speed_schedule.shape[0]} rows, this rank's ids reach "
+                             f"{id_offset + B - 1}")
+        rows = speed_schedule[ids]
+    if rows.shape != (B, T + N):
+        raise ValueError(f"speed_schedule: the rows of {B} ids must be [{B},{T + N}], got {rows.shape}")
+    return np.ascontiguousarray(rows)
+
+
 def _rank_stats(res, w, drop_failed):
     """(pooled [7,5], fails_total) of one rank's closed loop res on its workload w; drop_failed: over the trajectories
     without a failed step, the ones that are written."""
@@ -175,7 +202,8 @@ def _rank_stats(res, w, drop_failed):
     mask = None
     if drop_failed:
         mask = (torch.as_tensor(st) >= FAILED_STATUS).sum(dim=0) == 0
-    s = TB.closed_loop_stats(dict(X=res["X"], U=res["U"], status=st), w["paths"], w["vref"], w["u0"], mask=mask)
+    s = TB.closed_loop_stats(dict(X=res["X"], U=res["U"], status=st), w["paths"], w["vref"], w["u0"], mask=mask,
+                             vref_step=w.get("vref_step", 0))
     return s["pooled"], s["fails_total"]
 
 

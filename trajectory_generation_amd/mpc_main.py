@@ -10,7 +10,8 @@ Reference correspondence (DorianaG01/trajectory_generation, MPC/main.py):
                                   batch.closed_loop_stats
   format_statistics               the text of :113-121
 The plots and the GIF (:123-200) are out of scope, as everywhere in the package.  Like the script, simulate evaluates
-the speed profile at simulation time 0 on every step (:87 calls it with no time argument).
+the speed profile at simulation time 0 on every step (:87 calls it with no time argument); simulate(scheduled=True)
+samples it once over the whole run instead and slides the horizon's window along it, one sample per step.
 """
 from __future__ import annotations
 
@@ -55,28 +56,34 @@ _SCRIPT_X0 = x0
 
 
 def simulate(B=1, steps=sim_steps, N=N, Ts=Ts, profile=vref_profile_ramp_cruise, x0=None, path=(0, [0, 0, 0.1, 0]),
-             device=None) -> dict:
+             device=None, scheduled=False) -> dict:
     """The script's loop (main.py:85-101) for B trajectories in one fused launch, and its evaluation (:107-121).
 
     profile(N, Ts) -> vref [N+1] (one of the three above, or any callable of that form); x0 [6] or [B,6] (default: the
     script's, for every trajectory); path = (kind, [c0, c1, c2, c3]) as batch.PathSet takes it (default: the script's
     parabola y = 0.1 x^2) or a batch.PathSet of B paths.  u_prev starts at [d_steady_state(v0_target), 0] (:22).
+    scheduled=False (default): the script's loop, the profile's first N + 1 samples at every step.  True: the profile in
+    the run's own time -- profile(steps + N - 1, Ts), its steps + N samples one per Ts -- and step t reads samples
+    t .. t + N (run_closed_loop(vref_step=1)); e_v is then taken against the schedule (closed_loop_stats(vref_step=1)).
     Returns run_closed_loop's dict (X [B,steps+1,6], U [B,steps,2], status, iters, ...) with "stats": what
-    batch.closed_loop_stats returns for it, and "vref", "u0", "paths"."""
+    batch.closed_loop_stats returns for it, and "vref", "vref_step", "u0", "paths"."""
     from . import batch as TB
     dev = TB.require_gpu(device)
     B = int(B)
     xs = np.broadcast_to(np.asarray(_SCRIPT_X0 if x0 is None else x0, dtype=np.float64), (B, 6)).copy()
     u0 = np.tile(np.array([d_steady_state(v0_target), 0.0]), (B, 1))
-    vref = np.asarray(profile(N, Ts), dtype=np.float64).reshape(N + 1)
+    vref_step = 1 if scheduled else 0
+    L = int(steps) + N if scheduled else N + 1
+    vref = np.asarray(profile(L - 1, Ts), dtype=np.float64).reshape(L)
     if isinstance(path, TB.PathSet):
         paths = path
     else:
         kind, pc = path
         paths = TB.PathSet.build([int(kind)] * B, np.tile(np.asarray(pc, dtype=np.float64), (B, 1)), device=dev)
     run = TB.run_closed_loop(TB._dev(xs, None, dev), TB._dev(u0, None, dev), paths, vref, int(steps),
-                             TB.config_struct(N=N, Ts=Ts))
-    run.update(stats=TB.closed_loop_stats(run, paths, vref, u0), vref=vref, u0=u0, paths=paths)
+                             TB.config_struct(N=N, Ts=Ts), vref_step=vref_step)
+    run.update(stats=TB.closed_loop_stats(run, paths, vref, u0, vref_step=vref_step), vref=vref, vref_step=vref_step,
+               u0=u0, paths=paths)
     return run
 
 
