@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("TRAJMPC_LIB") or os.path.join(_HERE, "libtrajmpc.so")
 CSRC = os.path.join(_HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "trajmpc.h")
 HEADERS = [HEADER, os.path.join(os.path.dirname(_HERE), "include", "trajknet.h"),
-           os.path.join(os.path.dirname(_HERE), "include", "trajgen.h")]
+           os.path.join(os.path.dirname(_HERE), "include", "trajgen.h"),
+           os.path.join(os.path.dirname(_HERE), "include", "trajobs.h")]
 
 TRAJ_OK, TRAJ_E_ARG, TRAJ_E_UNSUPPORTED, TRAJ_E_LAUNCH, TRAJ_E_HANDOFF = 0, -1, -2, -3, -4
 MAX_N = 40            # the register-resident hot kernels' capacity (include/trajmpc.h TRAJ_MAX_N)
@@ -122,6 +123,15 @@ GEN_DEFAULT_FORM = GEN_FORM_DIRECT                           # TRAJ_GEN_DEFAULT_
 WORKLOADS = {"spline": 0, "mixed": 1, "parabola": 2}         # TRAJ_WORKLOAD_*
 WORKLOAD_SPLINE_KNOTS = 11                                   # TRAJ_WORKLOAD_SPLINE_KNOTS
 WORKLOAD_MAX_SEED_WORDS = 6                                  # TRAJ_WORKLOAD_MAX_SEED_WORDS
+
+
+OBS_TRUTH, OBS_EKF, OBS_EXTERNAL = 0, 1, 2   # TRAJ_OBS_* (include/trajobs.h)
+OBS_DEFAULT_LANES = 16                       # TRAJ_OBS_DEFAULT_LANES
+
+
+class ObsConfig(C.Structure):
+    """traj_obs_config (the closed loop on an estimate: the estimator and the EKF's Q, R)."""
+    _fields_ = [("estimator", C.c_int), ("Q", C.c_double * 6), ("R", C.c_double * 5)]
 
 
 class Paths(C.Structure):
@@ -264,6 +274,22 @@ _SIGS = {
                                              _V, _V, _V, _V, C.c_size_t, _V]),
     "traj_closed_loop_stats_sched": (C.c_int, [C.POINTER(Paths), C.c_int, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V,
                                                C.c_longlong, C.c_int, C.c_int, _V, _V, _V, _V]),
+    # the closed loop on a state estimate (include/trajobs.h)
+    "traj_closed_loop_obs_workspace_bytes": (C.c_size_t, [C.POINTER(MpcConfig), C.c_int]),
+    "traj_closed_loop_obs_step": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths),
+                                            C.POINTER(KnetLimits), C.POINTER(ObsConfig), C.c_int, _V, _V, _V, _V, _V,
+                                            C.c_longlong, C.c_int, C.c_int, _V, C.c_int, C.c_int, _V, _V, _V, _V, _V,
+                                            _V, _V, C.c_size_t, _V]),
+    "traj_closed_loop_obs_run": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Paths),
+                                           C.POINTER(KnetLimits), C.POINTER(ObsConfig), C.c_int, _V, _V, _V, _V, _V,
+                                           C.c_longlong, C.c_int, C.c_int, _V, C.c_int, C.c_int, C.c_int, _V, _V, _V,
+                                           _V, _V, _V, _V, C.c_size_t, _V]),
+    "traj_closed_loop_observe": (C.c_int, [C.POINTER(VehicleParams), C.c_double, C.POINTER(KnetLimits),
+                                           C.POINTER(ObsConfig), C.c_int, _V, _V, _V, _V, _V, C.c_int, C.c_int, _V, _V, _V,
+                                           _V, _V]),
+    "traj_ekf_step_f64": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_double, C.c_int, _V, _V, _V,
+                                    _V, _V, _V, _V]),
+    "traj_debug_obs_lanes": (C.c_int, [C.c_int]),
 }
 
 _lib = None

@@ -17,6 +17,7 @@ namespace {
 #include "knet_dense.h"     // the fused step's packed weights, dense layers and GRU cells
 #include "knet_fc2.h"       // FC2 in its three product modes
 #include "knet_step.h"      // the fused step's front, back and back-front kernels
+#include "knet_ekf_step.h"  // one float64 EKF step (shared with closed_obs.hip)
 #include "knet_ekf.h"       // the float64 EKF baseline
 
 inline int nblk(long long n, int t) { return (int)((n + t - 1) / t); }
