@@ -1,6 +1,7 @@
 // san_route.cpp -- csrc/mpc_route.h on the host under AddressSanitizer / UBSan: route() for every horizon -1 .. 1026,
 // with and without state bounds, under the four settings of the row-split switches, for the four entries (B = 1 and 7,
-// the step's linearization switch both ways), held to the invariants the entry points of trajmpc.hip rely on.
+// the step's linearization switch both ways), held to the invariants the entry points of trajmpc.hip rely on; and the
+// workspace layout (layout()) for B in {0, 1, 7, 4096} and every N in 1 .. 1024, held to its own.
 // Prints "san_route ok".
 #include <cstdio>
 #include <cstring>
@@ -75,7 +76,46 @@ static int check(const traj_mpc_config& c, bool bounds, const Switches& s, Entry
     return 0;
 }
 
+// the base part's layout: regions in ascending order that do not overlap, doubles 8-byte and ints 4-byte aligned, the
+// order B ints and the queue 2 B + 2, and the total what ws_base_bytes returns -- the parent's closed form
+static int check_layout(int B, int N) {
+#define REQUIRE_L(cond)                                                                \
+    do {                                                                               \
+        if (!(cond)) {                                                                 \
+            std::printf("san_route FAILED: layout: %s (B=%d N=%d)\n", #cond, B, N);    \
+            return 1;                                                                  \
+        }                                                                              \
+    } while (0)
+    const WsLayout w = layout(B, N);
+    const size_t b = (size_t)B, bn = b * (size_t)N, d = sizeof(double), i = sizeof(int);
+    // {offset, bytes, alignment} in the order of the workspace
+    const size_t reg[9][3] = {{w.A, bn * 36 * d, d},    {w.Bm, bn * 12 * d, d}, {w.g, bn * 6 * d, d},
+                              {w.xf, bn * 12 * d, d},   {w.warm, b * 4 * d, d}, {w.order, b * i, i},
+                              {w.q_count, i, i},        {w.q_err, i, i},        {w.q_done, b * i, i}};
+    REQUIRE_L(w.A == 0);
+    for (int k = 0; k < 9; ++k) {
+        REQUIRE_L(reg[k][0] % reg[k][2] == 0);
+        const size_t next = k + 1 < 9 ? reg[k + 1][0] : w.q_claimed;
+        REQUIRE_L(reg[k][0] + reg[k][1] <= next);                      // ascending, no overlap
+        REQUIRE_L(B == 0 || reg[k][1] == 0 || reg[k][0] < next);
+    }
+    REQUIRE_L(w.q_claimed % i == 0 && w.q_claimed + b * i <= w.total);
+    REQUIRE_L(w.q_count - w.order == b * i);                           // the order: B ints
+    REQUIRE_L(w.queue_bytes == (2 * b + 2) * i);                       // the queue: 2 B + 2 ints, from its counter
+    REQUIRE_L(w.q_count + w.queue_bytes == w.q_claimed + b * i);
+    REQUIRE_L(w.total % 8 == 0);
+    REQUIRE_L(w.total == ws_base_bytes(B, N));
+    REQUIRE_L(w.total == (66 * bn + 4 * b) * 8 + (((3 * b + 2) * 4 + 7) / 8) * 8);
+#undef REQUIRE_L
+    ++checked;
+    return 0;
+}
+
 int main() {
+    const int layout_batches[4] = {0, 1, 7, 4096};
+    for (int B : layout_batches)
+        for (int N = 1; N <= 1024; ++N)
+            if (check_layout(B, N)) return 1;
     const int pairs[4][2] = {{21, 64}, {41, 64}, {21, 0}, {41, 0}};
     const Entry entries[4] = {Entry::Step, Entry::Qp, Entry::ClosedStep, Entry::ClosedRun};
     const int batches[2] = {1, 7};
@@ -104,6 +144,6 @@ int main() {
             std::printf("san_route FAILED: invalid field accepted\n");
             return 1;
         }
-    std::printf("san_route ok: %lld routes\n", checked);
+    std::printf("san_route ok: %lld routes and layouts\n", checked);
     return 0;
 }

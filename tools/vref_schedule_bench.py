@@ -49,7 +49,7 @@ def main():
     w = make_workload(B, N, Ts, kind="spline", seed=0)
     paths = TB.PathSet.build(w["kinds"], w["pcs"], w["knots"])
     S = 1.5 + 0.5 * np.sin(2 * np.pi * (np.arange(T + N)[None, :] * Ts) / 6.0 + np.arange(B)[:, None])
-    Sd, x0, u0 = TB._dev(S, None, dev), TB._dev(w["x0"], None, dev), TB._dev(w["u0"], None, dev)
+    Sd, x0, u0 = TB.dev_f64(S, None, dev), TB.dev_f64(w["x0"], None, dev), TB.dev_f64(w["u0"], None, dev)
     cold, warm = TB.config_struct(N=N, Ts=Ts, warm_start=0), TB.config_struct(N=N, Ts=Ts)
     sync = torch.cuda.synchronize
 

@@ -76,7 +76,8 @@ def config_struct(N=20, Ts=0.02, q_c=6.0, q_phi=0.5, q_vx=0.5, R=None, Rd=None,
     return c
 
 
-def _dev(x, shape=None, device=None) -> torch.Tensor:
+def dev_f64(x, shape=None, device=None) -> torch.Tensor:
+    """x as a contiguous float64 tensor on the GPU (device, or the current one), reshaped if a shape is given."""
     dev = require_gpu(device)
     t = torch.as_tensor(x, dtype=torch.float64, device=dev)
     if shape is not None:
@@ -87,7 +88,7 @@ def _dev(x, shape=None, device=None) -> torch.Tensor:
 # ---------------------------------------------------------------- physics
 
 def tire_forces_batch(x, u, params=None) -> torch.Tensor:
-    x = _dev(x, (-1, 6)); u = _dev(u, (-1, 2))
+    x = dev_f64(x, (-1, 6)); u = dev_f64(u, (-1, 2))
     out = torch.empty((x.shape[0], 3), dtype=torch.float64, device=x.device)
     _lib.check(_lib.lib().traj_tire_forces_batch(C.byref(params_struct(params)), x.shape[0], _p(x), _p(u), _p(out),
                                                  _stream()), "traj_tire_forces_batch")
@@ -95,7 +96,7 @@ def tire_forces_batch(x, u, params=None) -> torch.Tensor:
 
 
 def f_cont_batch(x, u, params=None) -> torch.Tensor:
-    x = _dev(x, (-1, 6)); u = _dev(u, (-1, 2))
+    x = dev_f64(x, (-1, 6)); u = dev_f64(u, (-1, 2))
     out = torch.empty((x.shape[0], 6), dtype=torch.float64, device=x.device)
     _lib.check(_lib.lib().traj_f_cont_batch(C.byref(params_struct(params)), x.shape[0], _p(x), _p(u), _p(out),
                                             _stream()), "traj_f_cont_batch")
@@ -103,7 +104,7 @@ def f_cont_batch(x, u, params=None) -> torch.Tensor:
 
 
 def numerical_jacobian_batch(x, u, params=None, eps_x=1e-5, eps_u=1e-5):
-    x = _dev(x, (-1, 6)); u = _dev(u, (-1, 2))
+    x = dev_f64(x, (-1, 6)); u = dev_f64(u, (-1, 2))
     B = x.shape[0]
     Jx = torch.empty((B, 6, 6), dtype=torch.float64, device=x.device)
     Ju = torch.empty((B, 6, 2), dtype=torch.float64, device=x.device)
@@ -115,7 +116,7 @@ def numerical_jacobian_batch(x, u, params=None, eps_x=1e-5, eps_u=1e-5):
 
 
 def linearize_discretize_batch(xbar, ubar, Ts, params=None):
-    x = _dev(xbar, (-1, 6)); u = _dev(ubar, (-1, 2))
+    x = dev_f64(xbar, (-1, 6)); u = dev_f64(ubar, (-1, 2))
     B = x.shape[0]
     A = torch.empty((B, 6, 6), dtype=torch.float64, device=x.device)
     Bm = torch.empty((B, 6, 2), dtype=torch.float64, device=x.device)
@@ -127,7 +128,7 @@ def linearize_discretize_batch(xbar, ubar, Ts, params=None):
 
 
 def lateral_error_batch(X, Y, Xref, Yref, phiref) -> torch.Tensor:
-    ts = [_dev(v, (-1,)) for v in (X, Y, Xref, Yref, phiref)]
+    ts = [dev_f64(v, (-1,)) for v in (X, Y, Xref, Yref, phiref)]
     out = torch.empty_like(ts[0])
     _lib.check(_lib.lib().traj_lateral_error_batch(ts[0].shape[0], *[_p(t) for t in ts], _p(out), _stream()),
                "traj_lateral_error_batch")
@@ -160,9 +161,9 @@ def simulate_open_loop(x0, u_raw, gen_cfg: GenConfig, params=None) -> dict:
     """B open-loop trajectories in one launch (traj_gen_simulate_batch): slew limiter and output clip of
     generation_type1.py:131-137, :287-288 on u_raw [B,T,2], then the Euler loop of :70-84 from x0 [B,6].
     Returns torch.cuda tensors X [B,T+1,6] (X[:,0] = x0) and U [B,T,2] (the controls that were applied)."""
-    x0 = _dev(x0, (-1, 6))
+    x0 = dev_f64(x0, (-1, 6))
     B = x0.shape[0]
-    u_raw = _dev(u_raw, None, x0.device)
+    u_raw = dev_f64(u_raw, None, x0.device)
     if u_raw.dim() != 3 or u_raw.shape[0] != B or u_raw.shape[2] != 2:
         raise ValueError(f"u_raw must be [B,T,2] with B = {B}, got {tuple(u_raw.shape)}")
     T = u_raw.shape[1]
@@ -206,7 +207,7 @@ def simulate_piecewise(x0, rng_state, T, Ts=0.01, rules=None, params=None, want_
     rng_state [B,4] uint64: np.random.PCG64(seed + i).state as (state >> 64, state & M, inc >> 64, inc & M)
     (generation_type2.pcg64_states; or its int64 CUDA tensor of the same bits).  Returns torch.cuda tensors X [B,T+1,6], U [B,T,2], mode [B,T] uint8 (codes of
     _lib.FSM_MODES) and, with want_rng_state, rng_state [B,4] int64 (the bits of the uint64 words) after the last draw."""
-    x0 = _dev(x0, (-1, 6))
+    x0 = dev_f64(x0, (-1, 6))
     B, T = x0.shape[0], int(T)
     if torch.is_tensor(rng_state):      # already on the device (generation_type2.pcg64_states with a device)
         if tuple(rng_state.shape) != (B, 4) or rng_state.dtype != torch.int64:
@@ -306,7 +307,7 @@ def sized_workspace(nbytes: int, device, role: str = "closed_loop") -> torch.Ten
 
 
 def workspace(B: int, N: int, device, extra_bytes: int = 0, role: str = "closed_loop") -> torch.Tensor:
-    """sized_workspace of traj_mpc_workspace_bytes(B, N) + extra_bytes (the closed loop's: _closed_extra)."""
+    """sized_workspace of traj_mpc_workspace_bytes(B, N) + extra_bytes (the closed loop's: closed_extra)."""
     return sized_workspace(int(_lib.lib().traj_mpc_workspace_bytes(int(B), int(N))) + int(extra_bytes), device, role)
 
 
@@ -317,12 +318,12 @@ def mpc_step_batch(x0, u_prev, path_ref, vref, cfg: MpcConfig, params=None, out:
     Returns torch.cuda tensors: u_cmd [B,2], status [B] (int codes, see _lib.STATUS_STRINGS),
     objective [B], X_opt [B,6,N+1], U_opt [B,2,N], iters [B], polished [B]."""
     N = cfg.N
-    x0 = _dev(x0, (-1, 6))
+    x0 = dev_f64(x0, (-1, 6))
     B = x0.shape[0]
     dev = x0.device
-    u_prev = _dev(u_prev, (B, 2), dev)
-    path_ref = _dev(path_ref, (B, N + 1, 3), dev)
-    vref = _dev(vref, (B, N + 1), dev)
+    u_prev = dev_f64(u_prev, (B, 2), dev)
+    path_ref = dev_f64(path_ref, (B, N + 1, 3), dev)
+    vref = dev_f64(vref, (B, N + 1), dev)
     o = out if out is not None else _outputs(B, N, dev)
     ws = sized_workspace(_lib.lib().traj_mpc_step_workspace_bytes(C.byref(cfg), B), dev, role="step")
     _lib.check(_lib.lib().traj_mpc_step_batch(
@@ -335,11 +336,11 @@ def mpc_step_batch(x0, u_prev, path_ref, vref, cfg: MpcConfig, params=None, out:
 def mpc_qp_batch(x0, u_prev, path_ref, vref, Ad, Bd, g, cfg: MpcConfig, params=None) -> dict:
     """The QP half of mpc_step (:180-275) with the linearization given: Ad [B,N,6,6], Bd [B,N,6,2], g [B,N,6]."""
     N = cfg.N
-    x0 = _dev(x0, (-1, 6))
+    x0 = dev_f64(x0, (-1, 6))
     B = x0.shape[0]
     dev = x0.device
-    args = [_dev(u_prev, (B, 2), dev), _dev(path_ref, (B, N + 1, 3), dev), _dev(vref, (B, N + 1), dev),
-            _dev(Ad, (B, N, 6, 6), dev), _dev(Bd, (B, N, 6, 2), dev), _dev(g, (B, N, 6), dev)]
+    args = [dev_f64(u_prev, (B, 2), dev), dev_f64(path_ref, (B, N + 1, 3), dev), dev_f64(vref, (B, N + 1), dev),
+            dev_f64(Ad, (B, N, 6, 6), dev), dev_f64(Bd, (B, N, 6, 2), dev), dev_f64(g, (B, N, 6), dev)]
     o = _outputs(B, N, dev)
     need = int(_lib.lib().traj_mpc_qp_workspace_bytes(C.byref(cfg), B))
     ws = sized_workspace(need, dev, role="step") if need else None   # (the register-resident kernels take none)
@@ -501,8 +502,8 @@ class PathSet:
         kind = torch.as_tensor(kinds, dtype=torch.int32, device=dev).reshape(-1).contiguous()
         B = kind.shape[0]
         nk = torch.as_tensor(nk, dtype=torch.int32, device=dev).reshape(-1).contiguous()
-        xk = _dev(xk, None, dev)
-        yk = _dev(yk, None, dev)
+        xk = dev_f64(xk, None, dev)
+        yk = dev_f64(yk, None, dev)
         if xk.dim() != 2 or xk.shape[0] != B or xk.shape[1] < 2 or yk.shape != xk.shape or nk.shape[0] != B:
             raise ValueError(f"xk, yk must be [B,kmax] with B = {B}, kmax >= 2 and nk [B]; got {tuple(xk.shape)}, "
                              f"{tuple(yk.shape)}, {tuple(nk.shape)}")
@@ -517,14 +518,14 @@ class PathSet:
                 b = int(bad[0])
                 raise ValueError(f"PathSet.build_device: trajectory {b}: nk = {int(nk[b])} with kmax = {kmax}, or its "
                                  "knots do not strictly increase, or a knot or ordinate is not finite")
-        return PathSet(kind=kind, pc=_dev(pcs, (B, 4), dev), nk=nk, xk=xk, coef=coef)
+        return PathSet(kind=kind, pc=dev_f64(pcs, (B, 4), dev), nk=nk, xk=xk, coef=coef)
 
 
 def ref_window_batch(paths: PathSet, x_start, vref, N, Ts) -> torch.Tensor:
     """MPC/main.py:51-68 for B trajectories -> path_ref [B,N+1,3]."""
-    xs = _dev(x_start, (-1,))
+    xs = dev_f64(x_start, (-1,))
     B = xs.shape[0]
-    vr = _dev(vref, (B, N + 1), xs.device)
+    vr = dev_f64(vref, (B, N + 1), xs.device)
     out = torch.empty((B, N + 1, 3), dtype=torch.float64, device=xs.device)
     ps = paths.struct()
     _lib.check(_lib.lib().traj_ref_window_batch(C.byref(ps), B, int(N), float(Ts), _p(xs), _p(vr), _p(out),
@@ -532,7 +533,7 @@ def ref_window_batch(paths: PathSet, x_start, vref, N, Ts) -> torch.Tensor:
     return out
 
 
-def _closed_extra(B: int, cfg: MpcConfig) -> int:
+def closed_extra(B: int, cfg: MpcConfig) -> int:
     """Bytes the closed loop needs past traj_mpc_workspace_bytes, by traj_closed_loop_workspace_bytes: the scratch of
     the long-horizon kernel or the general solver (with its window and u_cmd) where cfg runs on one of them."""
     L = _lib.lib()
@@ -540,49 +541,50 @@ def _closed_extra(B: int, cfg: MpcConfig) -> int:
     return max(0, need - int(L.traj_mpc_workspace_bytes(int(B), int(cfg.N))))
 
 
-def _schedule_shape(vref, B, vref_step, need, what):
-    """The speed schedule's checks, on shapes alone (no GPU): vref_step 0 or 1; with 1, vref [L] (one row for every
-    trajectory) or [B,L] with L >= need.  Returns (shared row?, L); raises ValueError."""
+_dev, _closed_extra = dev_f64, closed_extra   # their earlier, private names: callers written against them keep working
+
+
+def speed_reference(vref, B, N, device, vref_step, need, what):
+    """(tensor, vref_row, vref_len, vref_step) of the _sched entry points for either form of a speed reference.  Shapes
+    are checked first, on the host (ValueError); a contiguous float64 device tensor of the right shape passes untouched.
+    vref_step 0: vref [N+1] (expanded to B rows) or [B,N+1], the same every step -> ([B,N+1], N + 1, N + 1, 0).
+    vref_step 1: a schedule sampled at Ts, [L] (one shared row: vref_row = 0, never tiled) or [B,L], L >= need."""
     if vref_step not in (0, 1):
         raise ValueError(f"{what}: vref_step must be 0 (the same window every step) or 1 (a schedule sampled at Ts), "
                          f"got {vref_step!r}")
     shape = tuple(np.shape(vref))
+    ready = torch.is_tensor(vref) and vref.is_cuda and vref.dtype == torch.float64 and vref.is_contiguous()
+    if vref_step == 0:
+        if shape not in ((N + 1,), (1, N + 1), (B, N + 1)):
+            raise ValueError(f"{what}: vref must be [N+1] or [B,N+1] with B = {B}, N = {N}, got {shape}")
+        if not (ready and shape == (B, N + 1)):
+            vref = dev_f64(vref, (-1, N + 1), device)
+            if vref.shape[0] != B:
+                vref = vref.expand(B, N + 1).contiguous()
+        return vref, N + 1, N + 1, 0
     if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] != B):
         raise ValueError(f"{what}: a speed schedule is [L] or [B,L] with B = {B}, got {shape}")
     if shape[-1] < need:
         raise ValueError(f"{what}: the schedule holds {shape[-1]} samples, the call reads {need}")
-    return len(shape) == 1, int(shape[-1])
-
-
-def _schedule_args(vref, B, dev, vref_step, need, what):
-    """(tensor, vref_row, vref_len, vref_step) of the _sched entry points for a schedule vref [L] or [B,L]: a 1-D
-    schedule goes as one shared row (vref_row = 0), never tiled."""
-    shared, L = _schedule_shape(vref, B, vref_step, need, what)
-    vr = _dev(vref, None, dev)
-    return vr, (0 if shared else L), L, int(vref_step)
+    L = int(shape[-1])
+    return (vref if ready else dev_f64(vref, None, device)), (0 if len(shape) == 1 else L), L, 1
 
 
 def closed_loop_step(x, u_prev, paths: PathSet, vref, cfg: MpcConfig, params=None, t=0, hist_x=None, hist_u=None,
                      status=None, iters=None, vref_step=0):
     """One step of MPC/main.py:85-101 for all B trajectories; x [B,6], u_prev [B,2] updated in place.
     vref_step=1: vref is a speed schedule [L] or [B,L], L >= t + N + 1, and this step reads vref[b, t + k], k = 0..N
-    (traj_closed_loop_step_sched); 0 (default): vref [B,N+1], the same at every step."""
+    (traj_closed_loop_step_sched, which serves both forms); 0 (default): vref [N+1] or [B,N+1], the same at every
+    step."""
     B = x.shape[0]
-    if vref_step != 0:
-        _schedule_shape(vref, B, vref_step, int(t) + cfg.N + 1, "closed_loop_step")
+    vr, row, L, vs = speed_reference(vref, B, cfg.N, x.device, vref_step, int(t) + cfg.N + 1, "closed_loop_step")
     ps = paths.struct()
     T = hist_u.shape[1] if hist_u is not None else 0
-    ws = workspace(B, cfg.N, x.device, _closed_extra(B, cfg))
-    if vref_step != 0:
-        vr, row, L, vs = _schedule_args(vref, B, x.device, vref_step, int(t) + cfg.N + 1, "closed_loop_step")
-        _lib.check(_lib.lib().traj_closed_loop_step_sched(
-            C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vr), row, L, vs, int(t),
-            int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()),
-            "traj_closed_loop_step_sched")
-        return
-    _lib.check(_lib.lib().traj_closed_loop_step(
-        C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vref), int(t), int(T),
-        _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()), "traj_closed_loop_step")
+    ws = workspace(B, cfg.N, x.device, closed_extra(B, cfg))
+    _lib.check(_lib.lib().traj_closed_loop_step_sched(
+        C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vr), row, L, vs, int(t),
+        int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()),
+        "traj_closed_loop_step_sched")
 
 
 def closed_loop_run(x, u_prev, paths: PathSet, vref, cfg: MpcConfig, params=None, t0=0, steps=1, hist_x=None,
@@ -591,27 +593,21 @@ def closed_loop_run(x, u_prev, paths: PathSet, vref, cfg: MpcConfig, params=None
     to `steps` closed_loop_step calls; x, u_prev updated in place; status / iters [steps, B].
     check: synchronize and raise RuntimeError if the run lost an instance hand-off (traj_closed_loop_check).
     vref_step=1: vref is a speed schedule [L] or [B,L], L >= t0 + steps + N, and step t reads vref[b, t + k], k = 0..N
-    (traj_closed_loop_run_sched: still one launch); 0 (default): vref [B,N+1], the same at every step."""
+    (traj_closed_loop_run_sched, which serves both forms: still one launch); 0 (default): vref [N+1] or [B,N+1], the
+    same at every step."""
     B = x.shape[0]
-    if vref_step != 0:
-        _schedule_shape(vref, B, vref_step, int(t0) + int(steps) + cfg.N, "closed_loop_run")
+    vr, row, L, vs = speed_reference(vref, B, cfg.N, x.device, vref_step, int(t0) + int(steps) + cfg.N,
+                                     "closed_loop_run")
     ps = paths.struct()
     T = hist_u.shape[1] if hist_u is not None else 0
-    ws = workspace(B, cfg.N, x.device, _closed_extra(B, cfg))
-    if vref_step != 0:
-        vr, row, L, vs = _schedule_args(vref, B, x.device, vref_step, int(t0) + int(steps) + cfg.N, "closed_loop_run")
-        _lib.check(_lib.lib().traj_closed_loop_run_sched(
-            C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vr), row, L, vs,
-            int(t0), int(steps), int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8,
-            _stream()), "traj_closed_loop_run_sched")
-    else:
-        _lib.check(_lib.lib().traj_closed_loop_run(
-            C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vref), int(t0),
-            int(steps), int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8, _stream()),
-            "traj_closed_loop_run")
+    ws = workspace(B, cfg.N, x.device, closed_extra(B, cfg))
+    _lib.check(_lib.lib().traj_closed_loop_run_sched(
+        C.byref(params_struct(params)), C.byref(cfg), C.byref(ps), B, _p(x), _p(u_prev), _p(vr), row, L, vs,
+        int(t0), int(steps), int(T), _p(hist_x), _p(hist_u), _p(status), _p(iters), _p(ws), ws.numel() * 8,
+        _stream()), "traj_closed_loop_run_sched")
     if check:   # synchronizes: a lost instance hand-off raises instead of returning stale trajectories
         _lib.check(_lib.lib().traj_closed_loop_check(_p(ws), ws.numel() * 8, B, cfg.N, _stream()),
-                   "traj_closed_loop_run")
+                   "traj_closed_loop_run_sched")
 
 
 def run_closed_loop(x0, u0, paths: PathSet, vref, T, cfg: MpcConfig, params=None, record=True, fused=True,
@@ -623,19 +619,11 @@ def run_closed_loop(x0, u0, paths: PathSet, vref, T, cfg: MpcConfig, params=None
     the loop.  vref_step=1: vref is a speed schedule over the run, [L] (shared by all trajectories, passed as one row)
     or [B,L] with L >= T + N, sampled at Ts: step t takes vref[b, t : t + N + 1] for its window and its q_vx rows.
     Returns X [B,T+1,6] (X[:,0] = x0), U [B,T,2], status [T,B], iters [T,B] (torch.cuda)."""
-    if vref_step != 0:
-        _schedule_shape(vref, int(np.shape(x0)[0]) if len(np.shape(x0)) == 2 else 1, vref_step, int(T) + cfg.N,
-                        "run_closed_loop")
-    x = _dev(x0, (-1, 6)).clone()
-    B = x.shape[0]
+    B = int(np.shape(x0)[0]) if len(np.shape(x0)) == 2 else 1
+    vr = speed_reference(vref, B, cfg.N, None, vref_step, int(T) + cfg.N, "run_closed_loop")[0]
+    x = dev_f64(x0, (B, 6)).clone()
     dev = x.device
-    u = _dev(u0, (B, 2), dev).clone()
-    if vref_step != 0:
-        vr = _dev(vref, None, dev)
-    else:
-        vr = _dev(vref, (-1, cfg.N + 1), dev)
-        if vr.shape[0] == 1 and B > 1:
-            vr = vr.expand(B, cfg.N + 1).contiguous()
+    u = dev_f64(u0, (B, 2), dev).clone()
     hx = torch.empty((B, T + 1, 6), dtype=torch.float64, device=dev) if record else None
     hu = torch.empty((B, T, 2), dtype=torch.float64, device=dev) if record else None
     if record:
@@ -682,12 +670,14 @@ def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None, vref_ste
     X, U = run["X"], run["U"]
     if X is None or U is None:
         raise ValueError("closed_loop_stats needs the recorded histories (run_closed_loop(record=True))")
-    if vref_step != 0:
-        hT = int(np.shape(U)[1])
-        _schedule_shape(vref, int(np.shape(U)[0]), vref_step, (hT if T is None else int(T)) + 1, "closed_loop_stats")
-    X = _dev(X, None, X.device if torch.is_tensor(X) and X.is_cuda else None)
+    dev = X.device if torch.is_tensor(X) and X.is_cuda else None
+    # (a schedule's horizon only bounds the row's length: every N >= 1 with N + 1 <= L gives the same record)
+    N = 1 if vref_step != 0 else int((np.shape(vref) or (0,))[-1]) - 1
+    vr, row, L, vs = speed_reference(vref, int(np.shape(U)[0]), N, dev, vref_step,
+                                     (int(np.shape(U)[1]) if T is None else int(T)) + 1, "closed_loop_stats")
+    X = dev_f64(X, None, dev)
     dev = X.device
-    U = _dev(U, None, dev)
+    U = dev_f64(U, None, dev)
     B, hist_T = U.shape[0], U.shape[1]
     if U.dim() != 3 or U.shape[2] != 2 or tuple(X.shape) != (B, hist_T + 1, 6):
         raise ValueError(f"X must be [B,T+1,6] and U [B,T,2], got {tuple(X.shape)}, {tuple(U.shape)}")
@@ -696,18 +686,7 @@ def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None, vref_ste
         raise ValueError(f"paths holds {paths.B} trajectories, the run {B}")
     if B > 0 and not 1 <= T <= hist_T:
         raise ValueError(f"T = {T}: the statistics take 1 .. {hist_T} of the {hist_T} recorded steps")
-    u0 = _dev(u0, (B, 2), dev)
-    vr = _dev(vref, None, dev)
-    if vref_step != 0:
-        # (the horizon only bounds the row's length: every N >= 1 with N + 1 <= L gives the same record)
-        row, L, N = (0 if vr.dim() == 1 else vr.shape[-1]), vr.shape[-1], 1
-    else:
-        vr = vr.reshape(-1, vr.shape[-1])
-        if vr.shape[0] == 1 and B > 1:
-            vr = vr.expand(B, vr.shape[1]).contiguous()
-        if vr.shape[0] != B:
-            raise ValueError(f"vref must be [N+1] or [B,N+1] with B = {B}, got {tuple(vr.shape)}")
-        N = vr.shape[1] - 1
+    u0 = dev_f64(u0, (B, 2), dev)
     st = run.get("status")
     if st is not None:
         st = torch.as_tensor(st).to(device=dev, dtype=torch.int32).contiguous()
@@ -717,14 +696,9 @@ def closed_loop_stats(run, paths: PathSet, vref, u0, T=None, mask=None, vref_ste
     fails = torch.empty(B, dtype=torch.int32, device=dev)
     ps = paths.struct()
     with torch.cuda.device(dev):
-        if vref_step != 0:
-            _lib.check(_lib.lib().traj_closed_loop_stats_sched(
-                C.byref(ps), B, N, T, hist_T, _p(X), _p(U), _p(u0), _p(vr), row, L, int(vref_step), _p(st), _p(rec),
-                _p(fails), _stream()), "traj_closed_loop_stats_sched")
-        else:
-            _lib.check(_lib.lib().traj_closed_loop_stats(C.byref(ps), B, N, T, hist_T, _p(X), _p(U), _p(u0), _p(vr),
-                                                         _p(st), _p(rec), _p(fails), _stream()),
-                       "traj_closed_loop_stats")
+        _lib.check(_lib.lib().traj_closed_loop_stats_sched(
+            C.byref(ps), B, N, T, hist_T, _p(X), _p(U), _p(u0), _p(vr), row, L, vs, _p(st), _p(rec), _p(fails),
+            _stream()), "traj_closed_loop_stats_sched")
     pooled, fails_total = pool_stats(rec, fails, mask)
     return dict(per_traj=rec, fails=fails, pooled=pooled, fails_total=fails_total, **stats_views(pooled))
 
@@ -734,7 +708,7 @@ def pool_stats(per_traj, fails=None, mask=None) -> tuple:
     (traj_closed_loop_stats_pool), with the sum of their fails [B] (default: 0).  Returns (pooled [7,5] numpy,
     fails_total int): one copy of 288 bytes, which synchronises.  Nothing kept: n = 0, the other fields NaN."""
     S, F = len(STATS_SERIES), len(STATS_FIELDS)
-    rec = _dev(per_traj, (-1, S, F), per_traj.device if torch.is_tensor(per_traj) and per_traj.is_cuda else None)
+    rec = dev_f64(per_traj, (-1, S, F), per_traj.device if torch.is_tensor(per_traj) and per_traj.is_cuda else None)
     B, dev = rec.shape[0], rec.device
     if fails is not None:
         fails = torch.as_tensor(fails).to(device=dev, dtype=torch.int32).reshape(B).contiguous()

@@ -14,13 +14,14 @@
 #include <atomic>
 
 #include "../../include/trajobs.h"
+#include "mpc_host.h"   // launched, nblk
 #include "physics.h"
 
 namespace {
 
 #include "knet_ekf_step.h"   // KPd, veh_f, ekf_step
 
-using tgmpc::VP;
+using tgmpc::VP, tgmpc::launched, tgmpc::nblk;
 
 struct ObsArgs {
     VP p;      // the plant's parameters (f_cont)
@@ -280,8 +281,6 @@ __global__ __launch_bounds__(GROUP_LANES * GROUPS) void ekf_step_group_kernel(KP
     for (int e = g; e < 36; e += GROUP_LANES) Pg[36 * (size_t)b + e] = S[G_P + e];
 }
 
-inline unsigned nblk(int n, int t) { return (unsigned)((n + t - 1) / t); }
-inline int launched() { return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH; }
 
 KPd kpd_of(const traj_vehicle_params* p, const traj_knet_limits* lim) {
     return KPd{p->Cm1, p->Cm2, p->Cr0, p->Cr2, p->Br, p->Cr, p->Dr, p->Bf, p->Cf, p->Df, p->m, p->Iz, p->lf, p->lr,

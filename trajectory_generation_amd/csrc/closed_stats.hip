@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mpc_common.h"
+#include "mpc_host.h"
 
 namespace tgmpc {
 
@@ -247,16 +248,12 @@ static int stats_launch(const traj_paths* paths, int B, int N, int T, int hist_T
                         const double* hist_u, const double* u0, const double* vref, long long vref_row, int vref_step,
                         const int* status, double* rec, int* fails, void* stream) {
     using namespace tgmpc;
-    if (B < 0 || N < 1 || T < 1 || T > hist_T) return TRAJ_E_ARG;
-    if (!paths || !paths->kind || !paths->pc || (paths->kmax >= 2 && (!paths->nk || !paths->xk || !paths->coef)))
-        return TRAJ_E_ARG;
+    if (B < 0 || N < 1 || T < 1 || T > hist_T || !paths_ok(paths)) return TRAJ_E_ARG;
     if (B == 0) return TRAJ_OK;
     if (!hist_x || !hist_u || !u0 || !vref || !rec) return TRAJ_E_ARG;
-    const PathArgs pa{paths->kmax, paths->kind, paths->pc, paths->nk, paths->xk, paths->coef};
-    const unsigned grid = (unsigned)(((long long)B + ST_WAVES - 1) / ST_WAVES);
-    hipLaunchKernelGGL(closed_stats_kernel, dim3(grid), dim3(ST_BLOCK), 0, (hipStream_t)stream, pa, B, T, hist_T,
-                       hist_x, hist_u, u0, vref, vref_row, vref_step, status, rec, fails);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    hipLaunchKernelGGL(closed_stats_kernel, dim3(nblk(B, ST_WAVES)), dim3(ST_BLOCK), 0, (hipStream_t)stream,
+                       path_args(paths), B, T, hist_T, hist_x, hist_u, u0, vref, vref_row, vref_step, status, rec, fails);
+    return launched();
 }
 
 extern "C" {
@@ -288,7 +285,7 @@ int traj_closed_loop_stats_pool(int B, const double* rec, const int* fails, cons
     if (!rec || !pooled) return TRAJ_E_ARG;
     hipLaunchKernelGGL(closed_stats_pool_kernel, dim3(1), dim3(ST_BLOCK), 0, (hipStream_t)stream, B, rec, fails, mask,
                        pooled, fails_total);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 }  // extern "C"

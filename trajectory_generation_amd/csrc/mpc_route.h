@@ -63,12 +63,33 @@ inline int check_cfg(const traj_mpc_config* c) {
     return TRAJ_OK;
 }
 
-// A/B/g hand-off (54 N doubles), rollout record (12 N), warm-start record (4), closed-loop order
-// (1 int), fused-run step queue (counter, error flag, completed and claimed steps per instance); a multiple of 8
-inline size_t ws_base_bytes(int B, int N) {
-    return ((size_t)B * (size_t)N * 66 + (size_t)B * 4) * sizeof(double) +
-           ((((size_t)B * 3 + 2) * sizeof(int) + 7) & ~(size_t)7);
+// The base part of the workspace, as byte offsets from its start -- the one statement of where each region lies:
+//   doubles  A [B,N,36] | Bm [B,N,12] | g [B,N,6] (the linearization's hand-off) | xf [B,N,12] (the rollout record) |
+//            warm [B,4] (the warm-start records)
+//   ints     order [B] (the closed loop's solve order) | the fused run's step queue, queue_bytes from q_count:
+//            q_count (next work item) | q_err (error flag) | q_done [B] (steps completed) | q_claimed [B]
+// total is the base part's size, a multiple of 8.
+struct WsLayout {
+    size_t A, Bm, g, xf, warm, order, q_count, q_err, q_done, q_claimed, queue_bytes, total;
+};
+inline WsLayout layout(int B, int N) {
+    const size_t b = (size_t)B, bn = b * (size_t)N, d = sizeof(double), i = sizeof(int);
+    WsLayout w;
+    w.A = 0;
+    w.Bm = w.A + bn * 36 * d;
+    w.g = w.Bm + bn * 12 * d;
+    w.xf = w.g + bn * 6 * d;
+    w.warm = w.xf + bn * 12 * d;
+    w.order = w.warm + b * 4 * d;
+    w.q_count = w.order + b * i;
+    w.q_err = w.q_count + i;
+    w.q_done = w.q_err + i;
+    w.q_claimed = w.q_done + b * i;
+    w.queue_bytes = w.q_claimed + b * i - w.q_count;
+    w.total = (w.q_count + w.queue_bytes + 7) & ~(size_t)7;
+    return w;
 }
+inline size_t ws_base_bytes(int B, int N) { return layout(B, N).total; }
 // the row-split kernel's P scratch inside the workspace (after the base part): every horizon it can run, whatever the
 // routing, so that traj_mpc_workspace_bytes does not depend on a debug switch (+ 2 doubles: 16-byte alignment slack)
 inline size_t split_bytes(int B, int N) {

@@ -1,9 +1,9 @@
 // split_inst.hip -- the row-split kernel's instantiations (mpc_split.h) and their launches, in a translation unit of
 // their own so that it is compiled like the other register-resident solvers (no machine-level LICM: hoisting per-lane
 // values out of the sweep and ADMM loops keeps them live across the whole solve and spills).
-#include <atomic>
 #include <cstdint>
 
+#include "mpc_host.h"
 #include "mpc_split.h"
 
 namespace tgmpc {
@@ -21,7 +21,7 @@ template <int H, bool CLOSED, bool INLIN>
 static int launch_one(const KArgs& a, double* al, size_t per, hipStream_t st) {
     hipLaunchKernelGGL((solve_split_kernel<H, CLOSED, false, INLIN>), dim3(a.B), dim3(SplitCfg<H>::NT), 0, st, a, al,
                        per);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launched();
 }
 template <bool CLOSED, bool INLIN = false>
 static int launch_split_t(const KArgs& a, double* sws, hipStream_t st) {
@@ -34,34 +34,19 @@ static int launch_split_t(const KArgs& a, double* sws, hipStream_t st) {
 }
 
 // The fused closed loop (a.nsteps steps; the queue, order and lead set up by the caller): one workgroup per resident
-// slot (occupancy x CUs; at least ceil(B / TRAJ_FUSED_MAX_PER_WG), at most B), each with its own P scratch.  Per device
-// the slot count is asked of the occupancy API once.
+// slot (resident_slots and fused_grid of mpc_host.h), each with its own P scratch.
 template <int H>
 static int launch_fused_h(const KArgs& a, double* al, size_t per, hipStream_t st) {
-    // (atomics, as launch_long's attribute flags: concurrent callers on several host threads at worst ask twice)
-    static std::atomic<int> slots[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -3;
-    int nslots = slots[dev].load(std::memory_order_acquire);
-    if (!nslots) {
-        int nb = 0, ncu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_split_kernel<H, true, true>, SplitCfg<H>::NT, 0) !=
-                hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            return -3;
-        nslots = (nb < 1 ? 1 : nb) * (ncu < 1 ? 1 : ncu);
-        slots[dev].store(nslots, std::memory_order_release);
-    }
-    int G = a.fused_grid > 0 ? a.fused_grid : nslots;
-    if (G > a.B) G = a.B;
-    const int minG = (a.B + TRAJ_FUSED_MAX_PER_WG - 1) / TRAJ_FUSED_MAX_PER_WG;
-    if (G < minG) G = minG;
+    static PerDevice slots;
+    const int nslots = resident_slots(slots, solve_split_kernel<H, true, true>, SplitCfg<H>::NT);
+    if (!nslots) return TRAJ_E_LAUNCH;
+    const int G = fused_grid(nslots, a.B, a.fused_grid);
     if (a.dbg)   // the stamped instance (tools/split_phase.py)
         hipLaunchKernelGGL((solve_split_kernel<H, true, true, true, true>), dim3(G), dim3(SplitCfg<H>::NT), 0, st, a,
                            al, per);
     else
         hipLaunchKernelGGL((solve_split_kernel<H, true, true>), dim3(G), dim3(SplitCfg<H>::NT), 0, st, a, al, per);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launched();
 }
 
 int launch_split_step(const KArgs& a, double* sws, hipStream_t st, bool inlin) {

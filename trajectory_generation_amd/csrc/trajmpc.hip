@@ -1,7 +1,8 @@
 // trajmpc.hip -- C ABI of libtrajmpc.so (declared in include/trajmpc.h).
 //
-// Batched physics kernels (one thread per point) and the dispatch of the fused MPC kernel
-// (mpc_kernel.h) by horizon capacity.  Built for gfx950 only:
+// Batched physics kernels (one thread per point) and the dispatch of the MPC solve kernels by tier (mpc_route.h) and,
+// for the register-resident ones (mpc_solve.h), by horizon capacity; the host side of every launch is mpc_host.h's.
+// Built for gfx950 only:
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 
 #include "../../include/trajmpc.h"
 #include "mpc_common.h"
+#include "mpc_host.h"
 #include "mpc_frame.h"
 #include "mpc_general.h"
 #include "mpc_long.h"
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(1024) void order_kernel(const double* warm, int B, 
 // (profiles/r05_tiers.json) it ran N = 24 / 30 / 32 at 0.43 / 0.34 / 0.35 M steps/s against 0.56 / 0.47 / 0.46 M on
 // capacity 80, so there is none
 #define TGMPC_CAPACITIES(X) X(16) X(32) X(40) X(80)
-#define TGMPC_DECL(NNV) int launch_mpc_##NNV(const KArgs& a, hipStream_t st, int mode);
+#define TGMPC_DECL(NNV) int launch_mpc_##NNV(const KArgs& a, hipStream_t st, Mode mode);
 TGMPC_CAPACITIES(TGMPC_DECL)
 #undef TGMPC_DECL
 
@@ -189,17 +191,7 @@ static void launch_linearize(const KArgs& a, hipStream_t st, bool closed) {
     }
 }
 
-// workspace layout: A [B,N,36] | B [B,N,12] | g [B,N,6] | rollout record [B,N,12] | warm [B,4] | order int[B]
-static void carve_workspace(KArgs& a, void* ws, int B, int N) {
-    a.wsA = (double*)ws;
-    a.wsB = a.wsA + (size_t)B * N * 36;
-    a.wsg = a.wsB + (size_t)B * N * 12;
-    a.wsXF = a.wsg + (size_t)B * N * 6;
-    a.wsWarm = a.wsXF + (size_t)B * N * 12;
-    a.Ad = a.wsA; a.Bd = a.wsB; a.gd = a.wsg;
-}
-
-static int launch_mpc(const KArgs& a, hipStream_t st, int mode) {
+static int launch_mpc(const KArgs& a, hipStream_t st, Mode mode) {
     const int n = 2 * a.c.N;
 #define TGMPC_CASE(NNV) \
     if (n <= NNV) return launch_mpc_##NNV(a, st, mode);
@@ -218,7 +210,7 @@ static int launch_gen(const KArgs& a, double* gws, hipStream_t st) {
         hipLaunchKernelGGL(solve_gen_kernel<GEN_RMAX_SMALL>, dim3(a.B), dim3(GEN_NT), 0, st, a, gws, per);
     else
         hipLaunchKernelGGL(solve_gen_kernel<GEN_RMAX>, dim3(a.B), dim3(GEN_NT), 0, st, a, gws, per);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 // the long-horizon kernel (mpc_long.h): TRAJ_MAX_N < N <= TRAJ_MAX_N_LONG without state bounds; its per-instance
@@ -230,25 +222,21 @@ static int launch_long(const KArgs& a, double* lws, hipStream_t st) {
     const size_t per = long_ws_doubles(N);
     if (2 * N <= LONG_NKL) {
         const size_t lds = long_lds_bytes(N);
-        // the dynamic-LDS attribute is set once per device (it belongs to the function's per-device code object); the
-        // flags are atomics, so concurrent callers on several host threads at worst set it twice
-        static std::atomic<bool> attr[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return TRAJ_E_LAUNCH;
-        if (dev < 0 || dev >= 64 || !attr[dev].load(std::memory_order_acquire)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_long_kernel<true, CLOSED>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(LONG_NKL * LONG_NKL * sizeof(double))) != hipSuccess)
-                return TRAJ_E_LAUNCH;
-            if (dev >= 0 && dev < 64) attr[dev].store(true, std::memory_order_release);
-        }
+        // the dynamic-LDS attribute belongs to the function's per-device code object
+        static PerDevice attr;
+        if (!once_per_device(attr, [](int) {
+                return hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_long_kernel<true, CLOSED>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)(LONG_NKL * LONG_NKL * sizeof(double))) == hipSuccess;
+            }))
+            return TRAJ_E_LAUNCH;
         hipLaunchKernelGGL((solve_long_kernel<true, CLOSED>), dim3(a.B), dim3(LONG_NT), lds, st, a, lws, per);
     } else if (2 * N <= LONG_NT) {
         hipLaunchKernelGGL((solve_long_kernel<false, CLOSED>), dim3(a.B), dim3(LONG_NT), 0, st, a, lws, per);
     } else {   // 128 < N <= TRAJ_MAX_N_LONG: the 512-thread instance (round 6)
         hipLaunchKernelGGL((solve_long_kernel<false, CLOSED, LONG_NT2>), dim3(a.B), dim3(LONG_NT2), 0, st, a, lws, per);
     }
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 // the row-split kernel (mpc_split.h; split_inst.hip, its own translation unit built without machine LICM like the
@@ -266,9 +254,6 @@ int launch_split_fused(const KArgs& a, double* sws, hipStream_t st);
 #ifndef TGMPC_LEAD_PERMILLE
 #define TGMPC_LEAD_PERMILLE 100
 #endif
-static long long* g_dbg = nullptr;  // diagnostics buffer (traj_debug_set_stamps)
-static long long* g_dbg_items = nullptr;  // fused-run item timeline (traj_debug_set_item_stamps)
-static int g_fused_grid = 0;        // traj_debug_fused_grid
 // fused runs of at least this many steps use the 3-waves-per-SIMD kernel (capacity 40; 0 = never).  Round 3 measured
 // it ahead over long launches (200 steps: 14.35 M vs 13.51 M steps/s; behind at 20 and 100 steps, where a launch is
 // bound by its heaviest instances' chains); since round 4's arithmetic work the 2-wave instance matches it there
@@ -277,9 +262,6 @@ static int g_fused_grid = 0;        // traj_debug_fused_grid
 #ifndef TRAJ_FUSED_W3_MIN_STEPS
 #define TRAJ_FUSED_W3_MIN_STEPS 0
 #endif
-static int g_fused_waves = 0;       // traj_debug_fused_waves: 0 = by launch length, 2 or 3 = forced
-static int g_spin_limit = 1 << 22;  // traj_debug_spin_limit: polls before a fused hand-off is declared lost
-static int g_lead_steps = TGMPC_LEAD_STEPS, g_lead_permille = TGMPC_LEAD_PERMILLE;   // traj_debug_queue_lead
 // fused run: a workgroup that completes an instance's step takes the instance's next step itself while that step is
 // at most this many levels past the queue's draw front (mpc_solve.h); 0 = every item from the queue in its order.
 // Off by default: at N = 20 it only adds contention (8 levels: 11.9 M vs 12.8 M); at config 3 it moves where the
@@ -288,7 +270,22 @@ static int g_lead_steps = TGMPC_LEAD_STEPS, g_lead_permille = TGMPC_LEAD_PERMILL
 #ifndef TGMPC_RUN_AHEAD
 #define TGMPC_RUN_AHEAD 0
 #endif
-static int g_run_ahead = TGMPC_RUN_AHEAD;   // traj_debug_run_ahead
+// The debug switches that routing does not depend on.  Atomics, like the routing switches below; an entry point reads
+// them once (debug_switches) and nothing reads a g_* again during the call.
+struct Debug {
+    long long *dbg, *dbg_items;   // traj_debug_set_stamps (diagnostics buffer), _set_item_stamps (fused item timeline)
+    int fused_grid, fused_waves;  // traj_debug_fused_grid; _fused_waves: 0 = by launch length, 2 or 3 = forced
+    int spin_limit;               // traj_debug_spin_limit: polls before a fused hand-off is declared lost
+    int lead_steps, lead_permille, run_ahead;   // traj_debug_queue_lead, traj_debug_run_ahead
+};
+static std::atomic<long long*> g_dbg{nullptr}, g_dbg_items{nullptr};
+static std::atomic<int> g_fused_grid{0}, g_fused_waves{0}, g_spin_limit{1 << 22}, g_lead_steps{TGMPC_LEAD_STEPS},
+    g_lead_permille{TGMPC_LEAD_PERMILLE}, g_run_ahead{TGMPC_RUN_AHEAD};
+static Debug debug_switches() {
+    constexpr auto rlx = std::memory_order_relaxed;
+    return Debug{g_dbg.load(rlx),        g_dbg_items.load(rlx),  g_fused_grid.load(rlx),    g_fused_waves.load(rlx),
+                 g_spin_limit.load(rlx), g_lead_steps.load(rlx), g_lead_permille.load(rlx), g_run_ahead.load(rlx)};
+}
 // horizons up to which TRAJ_MAX_N < N runs the row-split kernel (mpc_split.h) instead of the long-horizon one
 // (traj_debug_split_max_n: 0 sends every N > TRAJ_MAX_N to the long-horizon kernel; the two agree to the step bars)
 static std::atomic<int> g_split_max_n{TRAJ_MAX_N_SPLIT};
@@ -311,16 +308,21 @@ static Switches switches() {
 // rollout | jac | order | solve on the launch stream
 static std::vector<hipEvent_t> g_ev;
 static int g_ev_used = 0;
-static inline void stamp(int k, hipStream_t st) {
-    if ((size_t)(5 * g_ev_used + k) < g_ev.size()) (void)hipEventRecord(g_ev[5 * g_ev_used + k], st);
-}
-// the step's last stamp: the next step records into the next five events
-static inline void stamp_last(hipStream_t st) {
-    stamp(4, st);
-    if ((size_t)(5 * g_ev_used + 4) < g_ev.size()) ++g_ev_used;
-}
-
-static inline unsigned nblk(int B, int bs) { return (unsigned)((B + bs - 1) / bs); }
+// One step's five events.  Phase k (0 rollout, 1 jac, 2 order, 3 solve) lies between events k and k + 1: a step path
+// calls begin(k) before the launches it counts into phase k, in ascending order, and end() after its last launch; the
+// events of the phases it skips are recorded back to back.
+struct Phases {
+    hipStream_t st;
+    int next = 0;
+    void begin(int k) {
+        for (; next <= k; ++next)
+            if ((size_t)(5 * g_ev_used + next) < g_ev.size()) (void)hipEventRecord(g_ev[5 * g_ev_used + next], st);
+    }
+    void end() {   // the step's last event: the next step records into the next five
+        begin(4);
+        if ((size_t)(5 * g_ev_used + 4) < g_ev.size()) ++g_ev_used;
+    }
+};
 
 }  // namespace tgmpc
 
@@ -331,37 +333,37 @@ extern "C" {
 int traj_abi_version(void) { return TRAJMPC_ABI_VERSION; }
 
 int traj_debug_set_stamps(long long* buf) {
-    g_dbg = buf;
+    g_dbg.store(buf, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
 int traj_debug_set_item_stamps(long long* buf) {
-    g_dbg_items = buf;
+    g_dbg_items.store(buf, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
 int traj_debug_fused_grid(int workgroups) {
     if (workgroups < 0) return TRAJ_E_ARG;
-    g_fused_grid = workgroups;
+    g_fused_grid.store(workgroups, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
 int traj_debug_fused_waves(int waves) {
     if (waves < 0 || waves > 3) return TRAJ_E_ARG;
-    g_fused_waves = waves;
+    g_fused_waves.store(waves, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
 int traj_debug_queue_lead(int steps, int per_mille) {
     if (steps < 0 || per_mille < 0 || per_mille > 1000) return TRAJ_E_ARG;
-    g_lead_steps = steps;
-    g_lead_permille = per_mille;
+    g_lead_steps.store(steps, std::memory_order_relaxed);
+    g_lead_permille.store(per_mille, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
 int traj_debug_run_ahead(int levels) {
     if (levels < 0) return TRAJ_E_ARG;
-    g_run_ahead = levels;
+    g_run_ahead.store(levels, std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
@@ -385,7 +387,7 @@ int traj_debug_step_linearize(int in_kernel) {
 
 int traj_debug_spin_limit(int polls) {
     if (polls < 0) return TRAJ_E_ARG;
-    g_spin_limit = polls ? polls : (1 << 22);
+    g_spin_limit.store(polls ? polls : (1 << 22), std::memory_order_relaxed);
     return TRAJ_OK;
 }
 
@@ -476,7 +478,7 @@ int traj_tire_forces_batch(const traj_vehicle_params* p, int B, const double* x,
     if (!p || B < 0 || (B > 0 && (!x || !u || !out))) return TRAJ_E_ARG;
     if (B == 0) return TRAJ_OK;
     hipLaunchKernelGGL(tire_forces_kernel, dim3(nblk(B, 256)), dim3(256), 0, (hipStream_t)stream, *p, B, x, u, out);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 int traj_f_cont_batch(const traj_vehicle_params* p, int B, const double* x, const double* u, double* xdot,
@@ -484,7 +486,7 @@ int traj_f_cont_batch(const traj_vehicle_params* p, int B, const double* x, cons
     if (!p || B < 0 || (B > 0 && (!x || !u || !xdot))) return TRAJ_E_ARG;
     if (B == 0) return TRAJ_OK;
     hipLaunchKernelGGL(f_cont_kernel, dim3(nblk(B, 256)), dim3(256), 0, (hipStream_t)stream, *p, B, x, u, xdot);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 int traj_numerical_jacobian_batch(const traj_vehicle_params* p, int B, const double* x, const double* u,
@@ -493,7 +495,7 @@ int traj_numerical_jacobian_batch(const traj_vehicle_params* p, int B, const dou
     if (B == 0) return TRAJ_OK;
     hipLaunchKernelGGL(numjac_kernel, dim3(nblk(B, 128)), dim3(128), 0, (hipStream_t)stream, *p, B, x, u, eps_x,
                        eps_u, Jx, Ju, f);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 int traj_linearize_discretize_batch(const traj_vehicle_params* p, int B, double Ts, const double* xbar,
@@ -502,7 +504,7 @@ int traj_linearize_discretize_batch(const traj_vehicle_params* p, int B, double 
     if (B == 0) return TRAJ_OK;
     hipLaunchKernelGGL(lindisc_kernel, dim3(nblk(B, 128)), dim3(128), 0, (hipStream_t)stream, *p, B, Ts, xbar, ubar,
                        Ad, Bd, g);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 int traj_lateral_error_batch(int B, const double* X, const double* Y, const double* Xref, const double* Yref,
@@ -511,7 +513,7 @@ int traj_lateral_error_batch(int B, const double* X, const double* Y, const doub
     if (B == 0) return TRAJ_OK;
     hipLaunchKernelGGL(lateral_error_kernel, dim3(nblk(B, 256)), dim3(256), 0, (hipStream_t)stream, B, X, Y, Xref,
                        Yref, phiref, out);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    return launched();
 }
 
 // lin: the step (linearization in the library, `ws` holds its hand-off + the solver's scratch after it); !lin: the QP
@@ -528,35 +530,31 @@ static int mpc_common(const traj_vehicle_params* p, const traj_mpc_config* c, in
     if (!x0 || !u_prev || !path_ref || !vref || !u_cmd || !status) return TRAJ_E_ARG;
     if (!lin && (!Ad || !Bd || !g)) return TRAJ_E_ARG;
     if (r.need > 0 && (!ws || ws_bytes < r.need)) return TRAJ_E_ARG;
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.p = *p;
-    a.c = *c;
-    a.B = B;
+    KArgs a = kargs(p, c, B, debug_switches().dbg);
     a.x0 = x0; a.u_prev = u_prev; a.path_ref = path_ref; a.vref = vref;
     a.vref_row = c->N + 1;
     if (lin) {
-        carve_workspace(a, ws, B, c->N);
+        carve_workspace(a, ws, layout(B, c->N));
         a.wsWarm = nullptr;
     } else {
         a.Ad = Ad; a.Bd = Bd; a.gd = g;
     }
     a.u_cmd = u_cmd; a.status = status; a.objective = objective; a.X_opt = X_opt; a.U_opt = U_opt;
     a.iters = iters; a.polished = polished;
-    a.dbg = g_dbg;
-    // the step: one launch with the linearization in the workgroup (the register-resident kernels' mode 4, the
-    // row-split kernel's INLIN instance), or rollout_kernel + jac_kernel before the solve (traj_debug_step_linearize(0);
-    // the long-horizon and general solvers always read A/B/g from the workspace, as the QP entry point's solvers do)
+    // the step: one launch with the linearization in the workgroup (Mode::StepInlin of the register-resident kernels,
+    // the row-split kernel's INLIN instance), or rollout_kernel + jac_kernel before the solve
+    // (traj_debug_step_linearize(0); the long-horizon and general solvers always read A/B/g from the workspace, as the
+    // QP entry point's solvers do)
     hipStream_t st = (hipStream_t)stream;
     if (lin && !r.inlin) launch_linearize(a, st, false);
     double* const sws = (double*)((char*)ws + r.scratch_off);
     switch (r.tier) {
-        case Tier::Split: return launch_split_step(a, sws, st, r.inlin) ? TRAJ_E_LAUNCH : TRAJ_OK;
+        case Tier::Split: return launch_split_step(a, sws, st, r.inlin);
         case Tier::Long: return launch_long<false>(a, sws, st);
         case Tier::General: return launch_gen(a, sws, st);
         case Tier::Reg: break;
     }
-    return launch_mpc(a, st, lin ? (r.inlin ? 4 : 0) : 1);
+    return launch_mpc(a, st, !lin ? Mode::Qp : (r.inlin ? Mode::StepInlin : Mode::Step));
 }
 
 size_t traj_mpc_workspace_bytes(int B, int N) {
@@ -595,19 +593,14 @@ int traj_mpc_qp_batch(const traj_vehicle_params* p, const traj_mpc_config* c, in
                       polished, workspace, workspace_bytes, stream, false);
 }
 
-static bool paths_ok(const traj_paths* ps) {
-    return ps && ps->kind && ps->pc && (ps->kmax < 2 || (ps->nk && ps->xk && ps->coef));
-}
-
 int traj_ref_window_batch(const traj_paths* paths, int B, int N, double Ts, const double* x_start,
                           const double* vref, double* path_ref, void* stream) {
     if (B < 0 || N < 1 || !paths_ok(paths)) return TRAJ_E_ARG;
     if (B == 0) return TRAJ_OK;
     if (!x_start || !vref || !path_ref) return TRAJ_E_ARG;
-    PathArgs pa{paths->kmax, paths->kind, paths->pc, paths->nk, paths->xk, paths->coef};
-    hipLaunchKernelGGL(ref_window_kernel, dim3(nblk(B, 128)), dim3(128), 0, (hipStream_t)stream, pa, B, N, Ts,
-                       x_start, 1, vref, (long long)(N + 1), 0LL, path_ref);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    hipLaunchKernelGGL(ref_window_kernel, dim3(nblk(B, 128)), dim3(128), 0, (hipStream_t)stream, path_args(paths), B, N,
+                       Ts, x_start, 1, vref, (long long)(N + 1), 0LL, path_ref);
+    return launched();
 }
 
 // The closed loop by tier (mpc_route.h): the register-resident and row-split kernels fused (traj_closed_loop_run) or
@@ -617,14 +610,13 @@ int traj_ref_window_batch(const traj_paths* paths, int B, int N, double Ts, cons
 // one closed-loop step on the row-split or the long-horizon kernel (r.tier), on a's state (a.t = the step, a.status /
 // a.iters = this step's [B] rows): rollout_kernel + jac_kernel + the closed solve
 static int closed_step_long(const KArgs& a, const Route& r, void* ws, hipStream_t st) {
-    stamp(0, st);
+    Phases ph{st};
+    ph.begin(0);
     launch_linearize(a, st, true);
-    stamp(1, st);
-    stamp(2, st);
-    stamp(3, st);
+    ph.begin(3);
     double* const sws = (double*)((char*)ws + r.scratch_off);
     const int e = r.tier == Tier::Split ? launch_split_closed(a, sws, st) : launch_long<true>(a, sws, st);
-    stamp_last(st);
+    ph.end();
     return e;
 }
 
@@ -646,7 +638,8 @@ static int closed_step_sb(const KArgs& a0, const Route& r, void* ws, hipStream_t
     double* const pr = (double*)((char*)ws + r.scratch_off + r.scratch_bytes);
     double* const uc = pr + (size_t)B * 3 * (N + 1);
     int* const sbuf = (int*)(uc + (size_t)B * 2);
-    stamp(0, st);
+    Phases ph{st};
+    ph.begin(0);
     hipLaunchKernelGGL(ref_window_kernel, dim3(nblk(B, 128)), dim3(128), 0, st, a0.path, B, N, a0.c.Ts,
                        (const double*)a0.x_state, 6, a0.vref, a0.vref_row, (long long)a0.vref_step * a0.t, pr);
     KArgs a = a0;
@@ -659,29 +652,24 @@ static int closed_step_sb(const KArgs& a0, const Route& r, void* ws, hipStream_t
     a.wsWarm = nullptr;
     a.perm = nullptr;
     launch_linearize(a, st, false);
-    stamp(1, st);
-    stamp(2, st);
-    stamp(3, st);
+    ph.begin(3);
     int e = launch_gen(a, sws, st);
     if (e) return e;
     hipLaunchKernelGGL(closed_sb_plant_kernel, dim3(nblk(B, 64)), dim3(64), 0, st, a0, (const double*)uc);
-    stamp_last(st);
-    return hipGetLastError() == hipSuccess ? TRAJ_OK : TRAJ_E_LAUNCH;
+    ph.end();
+    return launched();
 }
 
 // the closed-loop entry points' kernel arguments: the loop's state, the paths, the history and the carved workspace
 static KArgs closed_args(const traj_vehicle_params* p, const traj_mpc_config* c, const traj_paths* paths, int B,
                          double* x, double* u_prev, const double* vref, long long vref_row, int vref_step, int t,
-                         int hist_T, double* hist_x, double* hist_u, int* status, int* iters, void* workspace) {
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.p = *p;
-    a.c = *c;
-    a.B = B;
+                         int hist_T, double* hist_x, double* hist_u, int* status, int* iters, void* workspace,
+                         const WsLayout& w, long long* dbg) {
+    KArgs a = kargs(p, c, B, dbg);
     a.vref = vref;
     a.vref_row = vref_row;
     a.vref_step = vref_step;
-    a.path = PathArgs{paths->kmax, paths->kind, paths->pc, paths->nk, paths->xk, paths->coef};
+    a.path = path_args(paths);
     a.x_state = x;
     a.u_state = u_prev;
     a.t = t;
@@ -690,8 +678,7 @@ static KArgs closed_args(const traj_vehicle_params* p, const traj_mpc_config* c,
     a.hist_u = hist_u;
     a.status = status;
     a.iters = iters;
-    a.dbg = g_dbg;
-    carve_workspace(a, workspace, B, c->N);
+    carve_workspace(a, workspace, w);
     return a;
 }
 
@@ -717,8 +704,9 @@ int traj_closed_loop_step_sched(const traj_vehicle_params* p, const traj_mpc_con
     if (!workspace || workspace_bytes < r.need) return TRAJ_E_ARG;
     if ((hist_x || hist_u) && (t < 0 || t >= hist_T)) return TRAJ_E_ARG;
     if (vref_step && t < 0) return TRAJ_E_ARG;
+    const WsLayout w = layout(B, c->N);
     KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, vref_row, vref_step, t, hist_T, hist_x, hist_u, status,
-                          iters, workspace);
+                          iters, workspace, w, debug_switches().dbg);
     hipStream_t st = (hipStream_t)stream;
     switch (r.tier) {
         case Tier::General: return closed_step_sb(a, r, workspace, st);
@@ -727,20 +715,21 @@ int traj_closed_loop_step_sched(const traj_vehicle_params* p, const traj_mpc_con
         case Tier::Reg: break;
     }
     const int nr = (B + 63) / 64, nj = (B * c->N + 63) / 64;
-    stamp(0, st);
+    Phases ph{st};
+    ph.begin(0);
     hipLaunchKernelGGL(rollout_kernel<true>, dim3(nr), dim3(64), 0, st, a);
-    stamp(1, st);
+    ph.begin(1);
     hipLaunchKernelGGL(jac_kernel<true>, dim3(nj), dim3(256), 0, st, a);
-    stamp(2, st);
+    ph.begin(2);
     if (t > 0) {
         // order this step's solves by the previous step's iteration counts (longest first)
-        int* perm = (int*)(a.wsWarm + (size_t)B * 4);
+        int* perm = (int*)((char*)workspace + w.order);
         hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, st, (const double*)a.wsWarm, B, perm, 2);
         a.perm = perm;
     }
-    stamp(3, st);
-    const int e = launch_mpc(a, st, 2);
-    stamp_last(st);
+    ph.begin(3);
+    const int e = launch_mpc(a, st, Mode::ClosedStep);
+    ph.end();
     return e;
 }
 
@@ -765,24 +754,26 @@ int traj_closed_loop_run_sched(const traj_vehicle_params* p, const traj_mpc_conf
     if (!x || !u_prev || !vref || t0 < 0) return TRAJ_E_ARG;
     if (!workspace || workspace_bytes < r.need) return TRAJ_E_ARG;
     if ((hist_x || hist_u) && t0 + steps > hist_T) return TRAJ_E_ARG;
+    const WsLayout w = layout(B, c->N);
+    const Debug d = debug_switches();
     KArgs a = closed_args(p, c, paths, B, x, u_prev, vref, vref_row, vref_step, t0, hist_T, hist_x, hist_u, status,
-                          iters, workspace);
+                          iters, workspace, w, d.dbg);
     a.nsteps = steps;
-    a.fused_grid = g_fused_grid;
+    a.fused_grid = d.fused_grid;
     // kernel instance: capacity 40, 2 waves per SIMD (3 from TRAJ_FUSED_W3_MIN_STEPS steps when that is set); capacity
     // 80, one wave per SIMD (the lean two-wave instance, traj_debug_fused_waves(2), spills at its 256 registers)
     constexpr int w3_min = TRAJ_FUSED_W3_MIN_STEPS;
     // (by the capacity launch_mpc picks: n = 2N > 40 runs capacity 80, so 20 < N <= 32 takes the one-wave-per-SIMD
     // instance too; until round 5 it fell through to the opt-in lean two-wave instance, which spills: N = 30 ran
     // 0.68 M against N = 40's 0.99 M)
-    a.wps = g_fused_waves ? g_fused_waves : (2 * c->N > 40 ? 1 : ((w3_min > 0 && steps >= w3_min) ? 3 : 2));
-    a.spin_limit = g_spin_limit;
-    a.dbg_items = g_dbg_items;
+    a.wps = d.fused_waves ? d.fused_waves : (2 * c->N > 40 ? 1 : ((w3_min > 0 && steps >= w3_min) ? 3 : 2));
+    a.spin_limit = d.spin_limit;
+    a.dbg_items = d.dbg_items;
     hipStream_t st = (hipStream_t)stream;
     // step queue: [0] next work item, [1] error flag, [2 + b] steps of instance b completed, [2 + B + b] claimed
-    a.queue = (int*)(a.wsWarm + (size_t)B * 4) + B;
-    if (hipMemsetAsync(a.queue, 0, ((size_t)B * 2 + 2) * sizeof(int), st) != hipSuccess) return TRAJ_E_LAUNCH;
-    a.run_ahead = g_run_ahead;
+    a.queue = (int*)((char*)workspace + w.q_count);
+    if (hipMemsetAsync(a.queue, 0, w.queue_bytes, st) != hipSuccess) return TRAJ_E_LAUNCH;
+    a.run_ahead = d.run_ahead;
     if (!r.fused) {
         // the long-horizon kernel or the general solver: the steps as step launch sequences, in order on the
         // stream (the same results as that many traj_closed_loop_step calls; the queue above stays clear, so
@@ -799,38 +790,32 @@ int traj_closed_loop_run_sched(const traj_vehicle_params* p, const traj_mpc_conf
         }
         return TRAJ_OK;
     }
-    stamp(0, st);
-    stamp(1, st);
-    stamp(2, st);
+    Phases ph{st};
+    ph.begin(2);
     if (t0 == 0) {
         // a run's first launch has no previous order, so order_kernel first runs on the SECOND launch; load
         // its code object now (HIP loads kernels lazily, ~0.75 ms of host time on the first launch) so that
         // cost is not paid inside a later, timed launch
         // (per device: HIP loads code objects per device; one process may drive several GPUs)
-        static std::atomic<bool> order_loaded[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !order_loaded[dev].load()) {
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&order_kernel)) == hipSuccess)
-                order_loaded[dev].store(true);
-        }
+        static PerDevice order_loaded;
+        (void)once_per_device(order_loaded, [](int) { return preload(&order_kernel); });
     }
     if (t0 > 0) {
         // instances ranked by their mean ADMM iterations per step in the previous launch; the kernel
         // pairs ranks heavy-with-light on each workgroup
-        int* perm = (int*)(a.wsWarm + (size_t)B * 4);
+        int* perm = (int*)((char*)workspace + w.order);
         hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, st, (const double*)a.wsWarm, B, perm, 3);
         a.perm = perm;
         // heavy instances lead the queue order (mpc_solve.h); none on a first launch (no previous order)
-        a.lead_steps = g_lead_steps;
-        a.lead_h = (int)(((long long)B * g_lead_permille) / 1000);
+        a.lead_steps = d.lead_steps;
+        a.lead_h = (int)(((long long)B * d.lead_permille) / 1000);
         if (a.lead_h >= B) a.lead_h = B - 1;
     }
-    stamp(3, st);
+    ph.begin(3);
     // the row-split kernel's fused instance (the same queue protocol), or the register-resident one
     const int e = r.tier == Tier::Split ? launch_split_fused(a, (double*)((char*)workspace + r.scratch_off), st)
-                                        : launch_mpc(a, st, 3);
-    stamp_last(st);
+                                        : launch_mpc(a, st, Mode::Fused);
+    ph.end();
     return e;
 }
 
@@ -847,10 +832,7 @@ int traj_closed_loop_check(const void* workspace, size_t workspace_bytes, int B,
     if (B < 0 || N < 1 || N > TRAJ_MAX_N_GENERAL) return TRAJ_E_ARG;
     if (B == 0) return TRAJ_OK;
     if (!workspace || workspace_bytes < traj_mpc_workspace_bytes(B, N)) return TRAJ_E_ARG;
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    carve_workspace(a, const_cast<void*>(workspace), B, N);
-    const int* flag = (const int*)(a.wsWarm + (size_t)B * 4) + B + 1;   // traj_closed_loop_run's queue[1]
+    const int* flag = (const int*)((const char*)workspace + layout(B, N).q_err);   // traj_closed_loop_run's queue[1]
     int h = 0;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return TRAJ_E_LAUNCH;

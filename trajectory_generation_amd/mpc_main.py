@@ -80,7 +80,7 @@ def simulate(B=1, steps=sim_steps, N=N, Ts=Ts, profile=vref_profile_ramp_cruise,
     else:
         kind, pc = path
         paths = TB.PathSet.build([int(kind)] * B, np.tile(np.asarray(pc, dtype=np.float64), (B, 1)), device=dev)
-    run = TB.run_closed_loop(TB._dev(xs, None, dev), TB._dev(u0, None, dev), paths, vref, int(steps),
+    run = TB.run_closed_loop(TB.dev_f64(xs, None, dev), TB.dev_f64(u0, None, dev), paths, vref, int(steps),
                              TB.config_struct(N=N, Ts=Ts), vref_step=vref_step)
     run.update(stats=TB.closed_loop_stats(run, paths, vref, u0, vref_step=vref_step), vref=vref, vref_step=vref_step,
                u0=u0, paths=paths)

@@ -18,8 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr as _p, stream as _stream
-from .batch import (MpcConfig, PathSet, _dev, _schedule_args, _schedule_shape, params_struct, require_gpu,
-                    sized_workspace)
+from .batch import MpcConfig, PathSet, dev_f64, params_struct, require_gpu, sized_workspace, speed_reference
 from .knet import EKF_P0, EKF_Q, EKF_R, limits_struct
 
 HR = (0, 1, 3, 4, 5)               # the measured rows of the state (vehicle_model.py:136-153)
@@ -77,27 +76,20 @@ class _Loop:
     """The buffers of one observed run and its two calls into the library."""
 
     def __init__(self, x0, u0, paths, vref, T, cfg, params, o, xhat0, noise, P0, vref_step):
-        x = _dev(x0, (-1, 6))
+        # (first: a bad reference is a ValueError before anything touches the GPU)
+        self.vr, self.row, self.L, self.vs = speed_reference(vref, int(np.shape(x0)[0]), cfg.N, None, vref_step,
+                                                             int(T) + cfg.N, "run_closed_loop_observed")
+        x = dev_f64(x0, (-1, 6))
         dev = x.device
         f64 = dict(dtype=torch.float64, device=dev)
         self.B, self.T, self.cfg, self.paths, self.o, self.dev = x.shape[0], int(T), cfg, paths, o, dev
         B = self.B
         self.x0 = x.clone()
-        self.u0 = _dev(u0, (B, 2), dev).clone()
-        self.xhat0 = self.x0.clone() if xhat0 is None else _dev(xhat0, (B, 6), dev).clone()
+        self.u0 = dev_f64(u0, (B, 2), dev).clone()
+        self.xhat0 = self.x0.clone() if xhat0 is None else dev_f64(xhat0, (B, 6), dev).clone()
         P0t = torch.as_tensor(np.asarray(P0, dtype=np.float64), **f64)
         self.P0 = (torch.diag_embed(P0t.expand(B, 6)) if P0t.dim() == 1 else P0t).contiguous().clone()
-        self.noise = None if noise is None else _dev(noise, (B, self.T, 5), dev)
-        if vref_step != 0:
-            self.vr, self.row, self.L, self.vs = _schedule_args(vref, B, dev, vref_step, self.T + cfg.N,
-                                                                "run_closed_loop_observed")
-        else:
-            vr = _dev(vref, (-1, cfg.N + 1), dev)
-            if vr.shape[0] == 1 and B > 1:
-                vr = vr.expand(B, cfg.N + 1).contiguous()
-            if vr.shape[0] != B:
-                raise ValueError(f"vref must be [N+1] or [B,N+1] with B = {B}, got {tuple(vr.shape)}")
-            self.vr, self.row, self.L, self.vs = vr, cfg.N + 1, cfg.N + 1, 0
+        self.noise = None if noise is None else dev_f64(noise, (B, self.T, 5), dev)
         self.p = params_struct(params)
         # (a missing limit is limits_struct's KeyError; no params at all misses the first)
         self.lim = limits_struct(params if isinstance(params, dict) else {}) if o.estimator == _lib.OBS_EKF else None
@@ -166,8 +158,6 @@ def run_closed_loop_observed(x0, u0, paths: PathSet, vref, T, cfg: MpcConfig, pa
     saw), Y [B,T,5] (Y[:,t] measures X[:,t+1]), U [B,T,2], status / iters [T,B], and the final x, xhat, u, P.
     closed_loop_stats takes the result as it takes run_closed_loop's."""
     B = _check_shapes(x0, u0, xhat0, noise, P0, T)
-    if vref_step != 0:
-        _schedule_shape(vref, B, vref_step, int(T) + cfg.N, "run_closed_loop_observed")
     external = callable(estimator)
     if external and graph:
         raise ValueError("graph=True captures library launches only: not with a callable estimator")
