@@ -17,7 +17,8 @@ CSRC = os.path.join(_HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "trajmpc.h")
 HEADERS = [HEADER, os.path.join(os.path.dirname(_HERE), "include", "trajknet.h"),
            os.path.join(os.path.dirname(_HERE), "include", "trajgen.h"),
-           os.path.join(os.path.dirname(_HERE), "include", "trajobs.h")]
+           os.path.join(os.path.dirname(_HERE), "include", "trajobs.h"),
+           os.path.join(os.path.dirname(_HERE), "include", "trajtrack.h")]
 
 TRAJ_OK, TRAJ_E_ARG, TRAJ_E_UNSUPPORTED, TRAJ_E_LAUNCH, TRAJ_E_HANDOFF = 0, -1, -2, -3, -4
 MAX_N = 40            # the register-resident hot kernels' capacity (include/trajmpc.h TRAJ_MAX_N)
@@ -132,6 +133,20 @@ OBS_DEFAULT_LANES = 16                       # TRAJ_OBS_DEFAULT_LANES
 class ObsConfig(C.Structure):
     """traj_obs_config (the closed loop on an estimate: the estimator and the EKF's Q, R)."""
     _fields_ = [("estimator", C.c_int), ("Q", C.c_double * 6), ("R", C.c_double * 5)]
+
+
+TRACK_DEFAULT_LANES = 16                     # TRAJ_TRACK_DEFAULT_LANES (include/trajtrack.h)
+TRACK_MAX_SAMPLES = 4096                     # TRAJ_TRACK_MAX_SAMPLES
+
+
+class Tracks(C.Structure):
+    """traj_tracks (closed tracks shared among the trajectories: periodic cubic splines by chord length)."""
+    _fields_ = [("n_tracks", C.c_int), ("kmax", C.c_int), ("nk", _V), ("sig", _V), ("coef", _V), ("track_of", _V)]
+
+
+class TrackSearch(C.Structure):
+    """traj_track_search (the projection's candidates, local reach and refinement count)."""
+    _fields_ = [("samples", C.c_int), ("back", C.c_double), ("fwd", C.c_double), ("newton", C.c_int)]
 
 
 class Paths(C.Structure):
@@ -290,6 +305,30 @@ _SIGS = {
     "traj_ekf_step_f64": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(KnetLimits), C.c_double, C.c_int, _V, _V, _V,
                                     _V, _V, _V, _V]),
     "traj_debug_obs_lanes": (C.c_int, [C.c_int]),
+    # the closed loop on closed tracks (include/trajtrack.h)
+    "traj_track_default_search": (C.c_int, [C.POINTER(TrackSearch)]),
+    "traj_track_project_batch": (C.c_int, [C.POINTER(Tracks), C.POINTER(TrackSearch), C.c_int, _V, C.c_longlong, _V, _V,
+                                           _V, _V]),
+    "traj_track_window_batch": (C.c_int, [C.POINTER(Tracks), C.c_int, C.c_int, C.c_double, _V, _V, _V, C.c_longlong,
+                                          C.c_int, C.c_longlong, _V, _V]),
+    "traj_track_project_host": (C.c_int, [C.POINTER(Tracks), C.POINTER(TrackSearch), C.c_int, _V, C.c_longlong, _V, _V,
+                                          _V]),
+    "traj_track_window_host": (C.c_int, [C.POINTER(Tracks), C.c_int, C.c_int, C.c_double, _V, _V, _V, C.c_longlong,
+                                         C.c_int, C.c_longlong, _V]),
+    "traj_closed_loop_track_workspace_bytes": (C.c_size_t, [C.POINTER(MpcConfig), C.c_int]),
+    "traj_closed_loop_track_step": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Tracks),
+                                              C.POINTER(TrackSearch), C.c_int, _V, _V, _V, _V, C.c_longlong, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, _V, _V, _V, _V, _V, _V, C.c_size_t, _V]),
+    "traj_closed_loop_track_run": (C.c_int, [C.POINTER(VehicleParams), C.POINTER(MpcConfig), C.POINTER(Tracks),
+                                             C.POINTER(TrackSearch), C.c_int, _V, _V, _V, _V, C.c_longlong, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, _V, _V, _V, _V, _V, _V, C.c_size_t,
+                                             _V]),
+    "traj_closed_loop_track_window": (C.c_int, [C.POINTER(Tracks), C.POINTER(TrackSearch), C.c_int, C.c_int, C.c_double,
+                                                _V, _V, _V, C.c_longlong, C.c_int, C.c_longlong, _V, _V, _V]),
+    "traj_closed_loop_track_plant": (C.c_int, [C.POINTER(VehicleParams), C.c_double, C.c_int, _V, _V, _V, _V, C.c_int,
+                                               C.c_int, _V, _V, _V, _V]),
+    "traj_track_errors_batch": (C.c_int, [C.POINTER(Tracks), C.c_int, C.c_int, _V, _V, _V, _V]),
+    "traj_debug_track_lanes": (C.c_int, [C.c_int]),
 }
 
 _lib = None

@@ -81,6 +81,13 @@ def _closed_loop_gpu(w, T, cfg):
     return TB.run_closed_loop(w["x0"], w["u0"], paths, w["vref"], T, cfg, vref_step=w.get("vref_step", 0))
 
 
+def _closed_loop_track_gpu(w, T, cfg):
+    """This rank's closed loop on closed tracks on the GPU (track.run_closed_loop_track)."""
+    from .. import track as TK
+    tracks = TK.TrackSet.build(w["knots"], w["track_of"])
+    return TK.run_closed_loop_track(w["x0"], w["u0"], tracks, w["vref"], T, cfg)
+
+
 def _run_rank(run, B, out_prefix, dist, shards, write):
     """What every generator does around its own computation.  run(id_offset) -> this rank's (X, U, status) for the
     ids rank * B .. rank * B + B - 1; write(prefix, X, U, status, ids) writes one set of files.  shards: this rank
@@ -138,10 +145,17 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
       trajectory id i) or a callable (ids, T, N, Ts) -> [len(ids),T+N].  Each rank takes the rows of its ids; its
       workload then carries vref [B,T+N] and vref_step = 1, step t reads vref[b, t : t + N + 1]
       (batch.run_closed_loop(vref_step=1)), and the statistics' e_v is taken against the schedule.
+    kind="track": the trajectories drive on shared closed circuits (workload.make_track_workload, eight 16-knot tracks;
+      track.run_closed_loop_track, one launch sequence per step), so phi covers every heading and winds past +-pi.  The
+      CSV schema, the sidecar, the sharding and the gather are the other kinds'.  stats=True, speed_schedule and
+      device_workload raise ValueError with it, and there is no fused single-launch loop on tracks yet.
     Returns (X [W B,T+1,6], U [W B,T,2], status [T,W B]) on rank 0 and None on the other ranks (shards:
     this rank's (X, U, status) everywhere)."""
-    from ..workload import make_workload, make_workload_device
+    from ..workload import make_track_workload, make_workload, make_workload_device
     _check_device_noise(device_csv, device_noise)
+    track = kind == "track"
+    if track and (stats or speed_schedule is not None or device_workload):
+        raise ValueError('kind="track" takes no stats, speed_schedule or device_workload yet')
     if speed_schedule is not None and not callable(speed_schedule):
         speed_schedule = np.asarray(speed_schedule, dtype=np.float64)
         if speed_schedule.ndim != 2 or speed_schedule.shape[1] != T + N:
@@ -152,14 +166,15 @@ def generate(B, T, N=20, Ts=0.05, kind="spline", seed=0, out_prefix=None, dist=N
     if closed_loop is None:
         from .. import batch as TB
         cfg = TB.config_struct(N=N, Ts=Ts, polish_mode=polish_mode)
-        closed_loop = _closed_loop_gpu
+        closed_loop = _closed_loop_track_gpu if track else _closed_loop_gpu
     if shards and drop_failed:
         raise ValueError("drop_failed re-indexes the whole dataset: it needs the gather (shards=False)")
 
     pooled = []     # stats: this rank's (pooled record, failed steps)
 
     def run(id_offset):
-        w = build(B, N, Ts, kind=kind, seed=seed, id_offset=id_offset)
+        w = (make_track_workload(B, N, Ts, seed=seed, id_offset=id_offset) if track
+             else build(B, N, Ts, kind=kind, seed=seed, id_offset=id_offset))
         if speed_schedule is not None:
             w["vref"], w["vref_step"] = _rank_schedule(speed_schedule, id_offset, B, T, N, Ts), 1
         if stats and w.get("paths") is None:

@@ -18,6 +18,8 @@ omega ~ U(-1, 1); u_prev = [d_ss(vx), 0] (main.py:20-22).  vref = the main.py:28
 (0.8 -> 2.0 m/s over 2 s) over the horizon, re-used every step (main.py:87).
 Trajectory `tid` draws from numpy.random.default_rng([seed, tid]) so shards are reproducible
 for any rank count.
+make_track_workload puts the trajectories on shared closed circuits instead (track.TrackSet): headings
+all round the compass, which no y(x) path gives.
 make_workload is the specification; make_workload_device builds the same workload and its PathSet on the GPU in
 one launch (csrc/workload.hip: the same streams and draws, no per-trajectory Python), opt-in.
 """
@@ -88,6 +90,50 @@ def make_workload(B, N=20, Ts=0.05, kind="spline", seed=0, id_offset=0):
     u0 = np.stack([np.array([d_steady_state(v), 0.0]) for v in x0[:, 3]])
     return dict(kinds=np.array(kinds, np.int32), pcs=np.array(pcs, np.float64), knots=knots, x0=x0, u0=u0,
                 vref=vref_ramp(N, Ts), ids=np.arange(id_offset, id_offset + B))
+
+
+def track_knots(seed, i, knots=16):
+    """Circuit i of make_track_workload, [knots,2], from numpy.random.default_rng([seed, i]): theta_j = 2 pi j / knots,
+    r_j = R0 (1 + a2 cos(2 theta_j + psi2) + a3 cos(3 theta_j + psi3)), knots (r cos theta, asp r sin theta) with
+    R0 ~ U(1.5, 2.5), a2, a3 ~ U(0, 0.12), psi2, psi3 ~ U(0, 2 pi), asp ~ U(0.6, 1), drawn in that order; an odd i has
+    its knots reversed (a clockwise track)."""
+    rng = np.random.default_rng([seed, i])
+    R0, a2, a3 = rng.uniform(1.5, 2.5), rng.uniform(0.0, 0.12), rng.uniform(0.0, 0.12)
+    psi2, psi3, asp = rng.uniform(0.0, 2 * np.pi), rng.uniform(0.0, 2 * np.pi), rng.uniform(0.6, 1.0)
+    th = 2.0 * np.pi * np.arange(knots) / knots
+    r = R0 * (1.0 + a2 * np.cos(2.0 * th + psi2) + a3 * np.cos(3.0 * th + psi3))
+    P = np.stack([r * np.cos(th), asp * r * np.sin(th)], axis=1)
+    return np.ascontiguousarray(P[::-1]) if i % 2 else P
+
+
+def make_track_workload(B, N=20, Ts=0.02, seed=0, n_tracks=8, knots=16, id_offset=0):
+    """B trajectories on n_tracks shared closed circuits (track.TrackSet; the loop is track.run_closed_loop_track).
+
+    Track i: track_knots(seed, i, knots) -- the same circuits whatever B and id_offset are.  Trajectory tid = id_offset
+    + b drives on track tid % n_tracks and draws from numpy.random.default_rng([seed, n_tracks + tid]), in this order: a
+    uniform place s on its track, a lateral offset U(-0.1, 0.1) m along the left normal, a heading offset U(-0.2, 0.2)
+    rad from the track's, v ~ U(0.8, 1.5) (vx = vref = v, held constant over the run), vy ~ U(-0.05, 0.05),
+    omega ~ U(-1, 1); u0 = (d_steady_state(v), 0).
+    Returns dict(knots: list of [knots,2], track_of [B], s0 [B], x0 [B,6], u0 [B,2], vref [B,N+1], ids [B])."""
+    from .track import TrackSet
+    if int(n_tracks) < 1 or int(knots) < 3 or int(B) < 0:
+        raise ValueError(f"need n_tracks >= 1, knots >= 3, B >= 0; got {n_tracks}, {knots}, {B}")
+    kn = [track_knots(seed, i, knots) for i in range(n_tracks)]
+    ts = TrackSet.build(kn)
+    ids = np.arange(id_offset, id_offset + B)
+    track_of = (ids % n_tracks).astype(np.int32)
+    x0, s0 = np.zeros((B, 6)), np.zeros(B)
+    for b, tid in enumerate(ids):
+        rng = np.random.default_rng([seed, n_tracks + int(tid)])
+        i = int(track_of[b])
+        s0[b] = rng.uniform(0.0, ts.L[i])
+        X, Y, dX, dY = (float(v) for v in ts.eval_host(i, s0[b]))
+        nrm = np.hypot(dX, dY)
+        off = rng.uniform(-0.1, 0.1)
+        x0[b] = [X - off * dY / nrm, Y + off * dX / nrm, np.arctan2(dY, dX) + rng.uniform(-0.2, 0.2),
+                 rng.uniform(0.8, 1.5), rng.uniform(-0.05, 0.05), rng.uniform(-1.0, 1.0)]
+    u0 = np.stack([np.array([d_steady_state(v), 0.0]) for v in x0[:, 3]]) if B else np.zeros((0, 2))
+    return dict(knots=kn, track_of=track_of, s0=s0, x0=x0, u0=u0, vref=np.repeat(x0[:, 3:4], N + 1, axis=1), ids=ids)
 
 
 def _workload_args(B, kind, seed, id_offset):
