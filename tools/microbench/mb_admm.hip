@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../../trajectory_generation_amd/csrc/mpc_common.h"
@@ -16,19 +17,32 @@ constexpr int NN = 40;
 
 // V 0: bcast = ds_write + __syncthreads (current); 1: ds_write + compiler fence only (one wave: LDS
 // executes a wave's DS instructions in order); 2: as 1 with one DPP per exchange (cost probe, not
-// equivalent); 3: Kmul only; 4: everything but Kmul
+// equivalent); 3: Kmul only; 4: everything but Kmul; 7: the kernel's contracted iteration with the row-form Kmul (4
+// chains); 8: the same with the class-form Kmul of TGMPC_KMUL_64 (160 chains over 64 lanes, partial sums through LDS);
+// 9 / 10: the row-form (4 chains) / class-form Kmul alone
 template <int V>
 __global__ __launch_bounds__(64) void admm_bench(const double* Kin, double* out, long long* cyc, int iters) {
-    __shared__ __attribute__((aligned(16))) double s_ex[4 * NN + 8];
+    constexpr int KCL = NN / 4, KPA = NN, KPB = KPA + 128, KPD = KPB + 128;   // (mpc_solve.h, K64)
+    constexpr bool CLS = V == 8 || V == 10;
+    __shared__ __attribute__((aligned(16))) double s_ex[KPD + 32 > 4 * NN + 8 ? KPD + 32 : 4 * NN + 8];
     const int t = threadIdx.x;
     const int n = NN;
     const bool own = t < n;
     const bool has_prev = (t >> 1) > 0;
-    for (int i = t; i < 4 * NN + 8; i += 64) s_ex[i] = 0.0;
+    for (int i = t; i < (int)(sizeof(s_ex) / 8); i += 64) s_ex[i] = 0.0;
     __syncthreads();
     double Krow[NN];
 #pragma unroll
-    for (int j = 0; j < NN; ++j) Krow[j] = own ? Kin[t * NN + j] : 0.0;
+    for (int j = 0; j < NN; ++j) Krow[j] = (own && !CLS) ? Kin[t * NN + j] : 0.0;
+    // class form: lane 16 c + m holds the columns = c mod 4 of rows 5 (m % 8) + m / 8 (+ 2; + 4 on the lanes m < 8)
+    const int lc = t >> 4, lm = t & 15, r0 = 5 * (lm & 7) + (lm >> 3);
+    double Kc[3][KCL];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+#pragma unroll
+        for (int i = 0; i < KCL; ++i) Kc[s][i] = (CLS && (s < 2 || lm < 8)) ? Kin[(r0 + 2 * s) * NN + lc + 4 * i] : 0.0;
+    }
+    const int kw0 = ((lc & 2) ? KPB : KPA) + 2 * r0 + (lc & 1), kw2 = (lm < 8) ? kw0 + 8 : KPD + 8 * lc + (lm & 7);
     const double a_b = 0.9 + 0.001 * t, a_r = 0.8 + 0.002 * t, a_rm = has_prev ? 0.7 : 0.0, a_rp = 0.75;
     const double rb = 0.1, rr = 0.12, rb_inv = 1.0 / rb, rr_inv = 1.0 / rr, sig = 1e-6, alpha = 1.6;
     const double slb = -0.5, sub = 0.5, slr = -0.05, sur = 0.05, qi = 0.01 * (t - 20);
@@ -41,6 +55,29 @@ __global__ __launch_bounds__(64) void admm_bench(const double* Kin, double* out,
         return own ? r : 0.0;
     };
     auto Kmul = [&](double v) -> double {
+        if (CLS) {
+            if (t < NN) s_ex[(t & 3) * KCL + (t >> 2)] = own ? v : 0.0;
+            __syncthreads();
+            const double2* v2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(s_ex + KCL * lc, 16));
+            double2 vc[KCL / 2];
+#pragma unroll
+            for (int i = 0; i < KCL / 2; ++i) vc[i] = v2[i];
+            double pa[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int i = 0; i < KCL / 2; ++i) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s) pa[s] = fma(Kc[s][2 * i], vc[i].x, pa[s]);
+#pragma unroll
+                for (int s = 0; s < 3; ++s) pa[s] = fma(Kc[s][2 * i + 1], vc[i].y, pa[s]);
+            }
+            s_ex[kw0] = pa[0];
+            s_ex[kw0 + 4] = pa[1];
+            s_ex[kw2] = pa[2];
+            __syncthreads();
+            const double2 pl = *reinterpret_cast<const double2*>(__builtin_assume_aligned(s_ex + KPA + 2 * t, 16));
+            const double2 ph = *reinterpret_cast<const double2*>(__builtin_assume_aligned(s_ex + KPB + 2 * t, 16));
+            return own ? (pl.x + pl.y) + (ph.x + ph.y) : 0.0;
+        }
         double* buf = s_ex + (xb & 3) * NN;
         xb++;
         if (own) buf[t] = v;
@@ -63,7 +100,7 @@ __global__ __launch_bounds__(64) void admm_bench(const double* Kin, double* out,
             for (int j = 0; j < NN; j += 8) s += vb[j];
             return own ? s : 0.0;
         }
-        if (V == 7) {
+        if (V == 7 || V == 9) {
             double s4[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int j = 0; j < NN; ++j) s4[j & 3] = fma(Krow[j], vb[j], s4[j & 3]);
@@ -86,11 +123,11 @@ __global__ __launch_bounds__(64) void admm_bench(const double* Kin, double* out,
     double x = 0.0, zb = 0.0, zr = 0.0, yb = 0.0, yr = 0.0;
     const long long t0 = __builtin_amdgcn_s_memtime();
     for (int it = 0; it < iters; ++it) {
-        if (V == 3 || V == 5 || V == 6) {
+        if (V == 3 || V == 5 || V == 6 || V == 9 || V == 10) {
             x = 0.5 * Kmul(x + qi) + 0.001;
             continue;
         }
-        if (V == 7) {
+        if (V == 7 || V == 8) {
             const double oma = 1.0 - alpha;
             const double wb = fma(rb, zb, -yb), wr = fma(rr, zr, -yr);
             const double wr_up = exch(wr, +2);
@@ -180,6 +217,16 @@ int main() {
         double md = 0;
         for (size_t i = 0; i < r0.size(); ++i) md = std::max(md, std::abs(r0[i] - r7[i]) / (1e-300 + std::abs(r0[i])));
         printf("  variant 7 vs 0: max rel diff %.3e\n", md);
+        std::vector<double> r8, r9, r10;
+        run<8>("contracted + class-form Kmul", nb, iters, dK, dout, dcyc, &r8);
+        run<9>("Kmul only, row form (4 chains)", nb, iters, dK, dout, dcyc, &r9);
+        run<10>("Kmul only, class form", nb, iters, dK, dout, dcyc, &r10);
+        size_t n87 = 0, n109 = 0;
+        for (size_t i = 0; i < r7.size(); ++i) {
+            n87 += (memcmp(&r8[i], &r7[i], 8) != 0);
+            n109 += (memcmp(&r10[i], &r9[i], 8) != 0);
+        }
+        printf("  variant 8 vs 7: %zu of %zu outputs differ in bits; 10 vs 9: %zu\n", n87, r7.size(), n109);
         size_t ndiff = 0;
         for (size_t i = 0; i < r0.size(); ++i) ndiff += (r0[i] != r1[i]);
         printf("  variant 1 vs 0: %zu of %zu outputs differ\n", ndiff, r0.size());

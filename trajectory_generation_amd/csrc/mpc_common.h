@@ -329,6 +329,25 @@ __device__ __forceinline__ void lds_load10_masked(unsigned a, unsigned long long
         : "memory");
 }
 
+// The same with five reads (80 bytes) into r[0..4]: a column class of a staged row (TGMPC_KMUL_64, mpc_solve.h).
+template <int OFF>
+__device__ __forceinline__ void lds_load5_masked(unsigned a, unsigned long long m, v2d_t* r) {
+    unsigned long long sv;
+    asm volatile(
+        "s_mov_b64 %[sv], exec\n\t"
+        "s_and_b64 exec, exec, %[m]\n\t"
+        "ds_read_b128 %[r0], %[a] offset:%[o0]\n\t"
+        "ds_read_b128 %[r1], %[a] offset:%[o1]\n\t"
+        "ds_read_b128 %[r2], %[a] offset:%[o2]\n\t"
+        "ds_read_b128 %[r3], %[a] offset:%[o3]\n\t"
+        "ds_read_b128 %[r4], %[a] offset:%[o4]\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(sv), [r0] "+v"(r[0]), [r1] "+v"(r[1]), [r2] "+v"(r[2]), [r3] "+v"(r[3]), [r4] "+v"(r[4])
+        : [a] "v"(a), [m] "s"(m), [o0] "i"(OFF + 0), [o1] "i"(OFF + 16), [o2] "i"(OFF + 32), [o3] "i"(OFF + 48), [o4] "i"(OFF + 64)
+        : "memory");
+}
+
 // ---- DPP cross-lane moves (gfx9 data-parallel primitives: VALU, no LDS traffic) -------------
 // CTRL: 0x130 wave_shl:1 (lane t receives lane t+1), 0x138 wave_shr:1 (lane t-1), 0xB1 / 0x4E
 // quad_perm [1,0,3,2] / [2,3,0,1], 0x141 row_half_mirror, 0x140 row_mirror, 0x142 row_bcast:15,

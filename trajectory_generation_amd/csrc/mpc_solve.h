@@ -57,6 +57,9 @@
 #ifndef TGMPC_SWEEP_2D
 #define TGMPC_SWEEP_2D 1       // fused capacity-40 instance at 2 waves per SIMD: K^-1 swept as 8 x 8 blocks of (NN/8)^2 entries, one
 #endif                         // block per lane, all 64 lanes busy (0: the row-per-lane receiver sweep); same values bit for bit
+#ifndef TGMPC_KMUL_64
+#define TGMPC_KMUL_64 1        // the same instance (needs TGMPC_SWEEP_2D): K^-1 v as 160 chains of 10 fma, one per (row, column
+#endif                         // class mod 4), dealt over all 64 lanes (0: 4 chains per row on lanes < NN); same values bit for bit
 #define TGMPC_PRAGMA_(x) _Pragma(#x)
 #define TGMPC_PRAGMA(x) TGMPC_PRAGMA_(x)
 #ifndef TGMPC_KCH80
@@ -135,6 +138,17 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     constexpr bool SW2D = TGMPC_SWEEP_2D && CMP && !LEAN && FULLP && NN == 40;
     constexpr int BSW = NN / 8;
     constexpr int ST2 = NN + 2;   // SW2D: row stride of the staging area that turns blocks back into rows
+    // K64: the ADMM / polish mat-vec K^-1 v by column class.  Row r's sum is four independent chains, chain c over the
+    // columns = c mod 4 in ascending order; lane 16 c + m runs chain c of up to three rows (slots), so all 64 lanes
+    // issue useful fma: 30 per mat-vec instead of 40, 5 broadcast reads instead of 20, 30 doubles of K^-1 instead of
+    // 40.  Row 5 q + k lives in lane m = q + 8 (k & 1) (k = 4: m = q), slot k / 2: lanes m < 8 hold three rows, the
+    // others two and an exact zero slot.  The four partial sums of a row go through LDS to lane r, which adds them in
+    // the row form's association -- the same operations on the same operands, so the same bits.
+    constexpr bool K64 = TGMPC_KMUL_64 && SW2D;
+    constexpr int KCL = NN / 4;                   // entries of a row per column class
+    constexpr int KPA = NN;                       // s_u: partials of classes 0, 1 at KPA + 2 r + c (after the vector)
+    constexpr int KPB = KPA + 2 * 64;             //      classes 2, 3 at KPB + 2 r + (c - 2); lanes >= NN read in bounds
+    constexpr int KPD = KPB + 2 * 64;             //      32 words nobody reads, for the absent slots' stores
     static_assert(!FULLP || (2 * PS) % 8 == 4, "conflict-free row stride");
     constexpr int NP = FULLP ? NN * PS : NP0;
     __shared__ double s_pref0[(CMP || L2W) ? 2 : 3 * (NM + 1)];
@@ -185,6 +199,7 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
     // SW2D: 8 staged rows of K^-1 (one local block row of every lane) in the region the sweep leaves dead
     constexpr int NU = (SW2D && 8 * ST2 > NU1) ? 8 * ST2 : NU1;
     __shared__ __attribute__((aligned(16))) double s_u[NU];
+    static_assert(!K64 || (KPD + 32 <= NU && KCL % 2 == 0 && KPA % 2 == 0), "K64: the partial sums' area");
     double* const s_ex = s_u;                     // exchange / broadcast buffers
     double* const s_sw = (CMP || L2W) ? s_u : s_u + NEX;   // sweep pivot columns (16-byte aligned: NEX is even)
     __shared__ __attribute__((aligned(16))) double s_F0[(CMP || WAVES > 1) ? 2 : NFS];
@@ -996,11 +1011,43 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
         };
         double Krow[NN];
         double Kb[SW2D ? BSW * BSW : 1];   // SW2D: the lane's block of K during the factorization, row-major
+        // K64: the lane's column class of up to three rows of K^-1 (slot s: Kc[5 s .. 5 s + 4], ascending columns), and
+        // where its partial sums go in s_u (kw0: slots 0 and 1, 4 words apart; kw2: slot 2, or a word nobody reads)
+        v2d_t Kc[K64 ? 3 * KCL / 2 : 1];
+        int kw0 = 0, kw2 = 0;
         auto Kmul = [&](double v, int slot = -1) -> double {  // (K^{-1} v)_t, KC independent FMA chains
             // (round 2 chose 4: one wave issues an f64 op about every 8 cycles, 8 chains measured far slower in the
             // fused instance, and at capacity 80 0.87 M vs 0.93 M at config 3, round 5; every instance of a capacity
             // uses the same chains, so fused and per-step stay bit-identical)
             constexpr int KC = 4;
+            if constexpr (K64) {
+                // lane t publishes v_t class-major (column j at (j % 4) KCL + j / 4; the padding 0.0 as in bcast), so a
+                // lane's class is KCL contiguous words; the chains start from +0.0 and run all KCL terms, like the row
+                // form's, whatever n is
+                if (t < NN) s_ex[(t & 3) * KCL + (t >> 2)] = own ? v : 0.0;
+                __syncthreads();
+                const double2* v2 = reinterpret_cast<const double2*>(__builtin_assume_aligned(s_ex + KCL * (t >> 4), 16));
+                double2 vc[KCL / 2];
+#pragma unroll
+                for (int i = 0; i < KCL / 2; ++i) vc[i] = v2[i];
+                double pa[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+                for (int i = 0; i < KCL / 2; ++i) {
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) pa[s] = fma(Kc[s * (KCL / 2) + i].x, vc[i].x, pa[s]);
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) pa[s] = fma(Kc[s * (KCL / 2) + i].y, vc[i].y, pa[s]);
+                }
+                s_u[kw0] = pa[0];
+                s_u[kw0 + 4] = pa[1];
+                s_u[kw2] = pa[2];
+                __syncthreads();
+                const double2 pl = *reinterpret_cast<const double2*>(__builtin_assume_aligned(s_u + KPA + 2 * t, 16));
+                const double2 ph = *reinterpret_cast<const double2*>(__builtin_assume_aligned(s_u + KPB + 2 * t, 16));
+                double r = (pl.x + pl.y) + (ph.x + ph.y);
+                asm volatile("" : "+v"(r));
+                return own ? r : 0.0;
+            }
             double sa[KC];
 #pragma unroll
             for (int i = 0; i < KC; ++i) sa[i] = 0.0;
@@ -1401,27 +1448,59 @@ __global__ __launch_bounds__(((NN + 63) / 64) * 64) __attribute__((amdgpu_waves_
 #pragma unroll
                 for (int i = 0; i < BSW * BSW; ++i) Kb[i] = -Kb[i];
                 static_assert(NN == 40, "the masked row read is written for 2 x 10 ds_read_b128");
-                const int rk = tq % BSW, rg = (tq < NN) ? tq / BSW : 0;
                 typedef __attribute__((address_space(3))) double* LdsD;
-                const unsigned ra = (unsigned)(__UINTPTR_TYPE__)(LdsD)(s_u + rg * ST2);
-                v2d_t kr[NN / 2];
+                if constexpr (K64) {
+                    // K64: the staged rows are class-major (column j at (j % 4) KCL + j / 4), and lane 16 c + m takes
+                    // the KCL entries of class c of staged row m % 8 -- in rounds 0 and 1 into slot 0 (lanes m < 8,
+                    // then m >= 8), rounds 2 and 3 into slot 1, round 4 into slot 2 (m < 8): a static slot and a
+                    // constant exec mask per round.  Slot 2 of the lanes m >= 8 keeps its exact zeros.
+                    static_assert(BSW == 5 && KCL == 10, "five staging rounds, five ds_read_b128 per class");
+                    const int lc = tq >> 4, lm = tq & 15;
+                    const unsigned ra = (unsigned)(__UINTPTR_TYPE__)(LdsD)(s_u + (lm & 7) * ST2 + KCL * lc);
+                    int wo[BSW];
 #pragma unroll
-                for (int i = 0; i < NN / 2; ++i) kr[i] = v2d_t{0.0, 0.0};
+                    for (int l = 0; l < BSW; ++l) {
+                        const int col = BSW * s + l;
+                        wo[l] = g * ST2 + (col & 3) * KCL + (col >> 2);
+                    }
 #pragma unroll
-                for (int k = 0; k < BSW; ++k) {
-                    __syncthreads();
-                    double* const wr = s_u + g * ST2 + BSW * s;
+                    for (int i = 0; i < 3 * KCL / 2; ++i) Kc[i] = v2d_t{0.0, 0.0};
 #pragma unroll
-                    for (int l = 0; l < BSW; ++l) wr[l] = Kb[k * BSW + l];
-                    __syncthreads();
-                    const unsigned long long rm = __ballot(rk == k);
-                    lds_load10_masked<0>(ra, rm, kr);
-                    lds_load10_masked<160>(ra, rm, kr + 10);
-                }
+                    for (int k = 0; k < BSW; ++k) {
+                        __syncthreads();
 #pragma unroll
-                for (int i = 0; i < NN / 2; ++i) {
-                    Krow[2 * i] = kr[i].x;
-                    Krow[2 * i + 1] = kr[i].y;
+                        for (int l = 0; l < BSW; ++l) s_u[wo[l]] = Kb[k * BSW + l];
+                        __syncthreads();
+                        const unsigned long long rm = (k & 1) ? 0xFF00FF00FF00FF00ull : 0x00FF00FF00FF00FFull;
+                        lds_load5_masked<0>(ra, rm, Kc + (k >> 1) * (KCL / 2));
+                    }
+                    // the partial sums' words: row 5 (m % 8) + m / 8 (slot 0), + 2 (slot 1), + 4 (slot 2, m < 8)
+                    const int r0 = BSW * (lm & 7) + (lm >> 3);
+                    kw0 = ((lc & 2) ? KPB : KPA) + 2 * r0 + (lc & 1);
+                    kw2 = (lm < 8) ? kw0 + 8 : KPD + 8 * lc + (lm & 7);
+                    asm volatile("" : "+v"(kw0), "+v"(kw2));
+                } else {
+                    const int rk = tq % BSW, rg = (tq < NN) ? tq / BSW : 0;
+                    const unsigned ra = (unsigned)(__UINTPTR_TYPE__)(LdsD)(s_u + rg * ST2);
+                    v2d_t kr[NN / 2];
+#pragma unroll
+                    for (int i = 0; i < NN / 2; ++i) kr[i] = v2d_t{0.0, 0.0};
+#pragma unroll
+                    for (int k = 0; k < BSW; ++k) {
+                        __syncthreads();
+                        double* const wr = s_u + g * ST2 + BSW * s;
+#pragma unroll
+                        for (int l = 0; l < BSW; ++l) wr[l] = Kb[k * BSW + l];
+                        __syncthreads();
+                        const unsigned long long rm = __ballot(rk == k);
+                        lds_load10_masked<0>(ra, rm, kr);
+                        lds_load10_masked<160>(ra, rm, kr + 10);
+                    }
+#pragma unroll
+                    for (int i = 0; i < NN / 2; ++i) {
+                        Krow[2 * i] = kr[i].x;
+                        Krow[2 * i + 1] = kr[i].y;
+                    }
                 }
             } else if constexpr (WAVES == 1) {
                 // One-wave sweep, ONE fma per entry and pivot.  The new pivot row (K_pj / d) is not
